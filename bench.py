@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Headline benchmark: shaded pixels/s and achieved HBM GB/s of the G-buffer shading pass.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C] [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: it builds the workload, ramps the clock, runs W warm-up and
+K timed steps, writes the last timed step's output when --dump-outputs is given, and prints the line. --full adds
+every other leg to the same line: the CPU baseline with its parity check of the timed frame, the scaling anchor,
+the gather timed alone with the band checksums, the assembled frame's parity at N > 1, and --exact-leg.
 
 N = 1: BASELINE config 3 -- a 3840x2160 G-buffer, 64 point lights + diffuse IBL (Chelsea_Stairs),
 one step = one shading pass over the whole frame (inputs resident in HBM before timing).
@@ -11,7 +16,7 @@ row band and the bands are gathered to rank 0 (pipelined: the gather of frame k 
 of frame k+1) as the presented R8G8B8A8_UNORM frame (--output; shading is fp32 at every N). Weak
 scaling: per-GPU work is fixed.
 
-Rank 0 prints one JSON line ("Measurement"). The cpu_baseline leg times the CPU
+Rank 0 prints one JSON line ("Measurement"). With --full the cpu_baseline leg times the CPU
 oracle (oracle/, test infrastructure) on a bounded row sample of the same frame and doubles as a
 parity check of the sampled rows.
 """
@@ -502,6 +507,29 @@ def clock_ramp(shade_into, out, ramp_ms: float) -> dict:
     return {"ms": round((time.perf_counter() - t0) * 1e3, 1), "launches": n}
 
 
+DUMP_BUDGET_BYTES = 60_000_000  # --dump-outputs: all files of one run together stay below 64 MB
+DUMP_SEED = 0
+
+
+def dump_outputs(path: str, arrays: dict) -> dict:
+    """--dump-outputs: write each (..., 4) device tensor of `arrays` as `path`/<name>.npy in float32 (RGBA8 codes as
+    their values 0..255). An output larger than its share of DUMP_BUDGET_BYTES is written as a fixed sample of its
+    pixels -- the sorted indices drawn by numpy's default_rng(DUMP_SEED), a function of the pixel count alone, so two
+    builds run with the same arguments write the same pixels -- as a (pixels, 4) array. Returns {name: shape}."""
+    os.makedirs(path, exist_ok=True)
+    keep = DUMP_BUDGET_BYTES // max(len(arrays), 1) // 16  # pixels per file: 4 channels of float32
+    shapes = {}
+    for name, t in arrays.items():
+        n = t.numel() // 4
+        if n > keep:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, keep, replace=False, shuffle=False))
+            t = t.reshape(n, 4)[torch.from_numpy(idx).to(t.device)]
+        a = t.to(torch.float32).cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
+
+
 def band_anchor(ctx, args, world: int, device, stream, resident=None) -> dict:
     """The scaling anchor: ONE rank's config-5 band (8192 x rows_per_rank, RGBA8, the run's mode) shaded alone
     -- no gather, no other rank -- timed like a step. It is the per-GPU work of every point of the 1/2/4/8-GPU
@@ -541,9 +569,19 @@ def main():
                          "settled GPU clocks (DVFS: the first ~40 ms of launches run 2.05 -> 1.75 ms, "
                          "profiles/r01 kernel trace); not a step, no gather")
     ap.add_argument("--config", type=int, default=0, help="BASELINE config id (default 3 at N=1, 5 at N>1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline and report it in the line: the CPU baseline and its "
+                         "parity check of the timed frame (N = 1), the scaling anchor, the gather timed alone and the "
+                         "band checksums (config 5), the assembled frame's parity (N > 1), --exact-leg. Without it the "
+                         "run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, rank 0 writes what the last timed step computed as DIR/<name>.npy "
+                         "(float32): `frame`, its shaded rows, and with config 5 `gathered_frame`, the image assembled "
+                         "from every rank's band. Below 64 MB in all: a larger output is written as a fixed, seeded "
+                         "sample of its pixels (dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline leg")
     ap.add_argument("--no-anchor", action="store_true",
-                    help="skip the scaling anchor (one rank's config-5 band shaded alone, scale_anchor)")
+                    help="--full without the scaling anchor (one rank's config-5 band shaded alone, scale_anchor)")
     ap.add_argument("--rows-per-rank", type=int, default=1024,
                     help="config 5 band height per rank (1024 = the BASELINE geometry: 8192x8192 at N = 8; "
                          "smaller only for rehearsing the multi-rank path). The same band at every N, N = 1 "
@@ -585,6 +623,10 @@ def main():
                          "build, PBR_* overrides): the line is printed with library.problems listed; without --dev such "
                          "a run exits 4 and prints no metric line")
     args = ap.parse_args()
+    if not args.full and (args.exact_leg or args.inject_parity_breach):
+        ap.error("--exact-leg and --inject-parity-breach belong to the legs that run with --full")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     # Which binary is measured (pbr_build_info): decided before anything runs, on any host.
     library = library_provenance(args.dev)
@@ -643,6 +685,15 @@ def main():
     ramp = clock_ramp(shade_into, outs[0], args.ramp_ms)
     elapsed, kernel_ms = shade_steps(shade_into, outs, stream, args.warmup, args.steps, gather, in_group)
 
+    # What the last timed step handed back, written before any other leg reuses the output slots.
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        arrays = {"frame": outs[(args.steps - 1) % 2][: band.rows]}
+        if gather is not None:
+            arrays["gathered_frame"] = gather.assembled(cfg.height)
+        dumped = dump_outputs(args.dump_outputs, arrays)
+        log(f"wrote {', '.join(f'{k}.npy {v}' for k, v in dumped.items())} to {args.dump_outputs}")
+
     # The executed work of the last timed pass (pbr_last_pass_stats; every timed pass shades the same input).
     stats = ctx.pass_stats(stream)
     kernel_name = ctx.last_kernel(stream)
@@ -653,7 +704,7 @@ def main():
 
     coll_dev = device if args.dist_backend == "nccl" else torch.device("cpu")
     gather_note = {}
-    if gather is not None:
+    if gather is not None and args.full:
         # The gather alone (no shading), timed the same way: the exchange cost the pipelined step hides.
         torch.cuda.synchronize()
         if in_group:
@@ -714,18 +765,20 @@ def main():
         cpu = None
         parity = {}
         exact_leg = None
-        frame = outs[0][: band.rows].cpu().numpy() if world == 1 else None  # the timed mode's frame
+        want_cpu = world == 1 and args.full and not args.no_cpu_baseline
+        frame = outs[0][: band.rows].cpu().numpy() if want_cpu else None  # the timed mode's frame
         if frame is not None and args.inject_parity_breach:  # test only: the largest channel, scaled
             frame = frame.copy()
             flat = frame.reshape(-1)
             k = int(np.argmax(np.where(np.isfinite(flat), np.abs(flat.astype(np.float64)), 0.0)))
             flat[k] = flat[k] * (1.0 + args.inject_parity_breach) if not rgba8 else (int(flat[k]) + 2) % 256
         exact_frame = None
-        assembled = gather.assembled(cfg.height).cpu().numpy() if world > 1 and gather is not None else None
+        assembled = (gather.assembled(cfg.height).cpu().numpy() if args.full and world > 1 and gather is not None
+                     else None)
         # The scaling anchor runs right after the timed steps, on a warm GPU, before the host-side legs (the CPU
         # baseline and the parity checks leave the GPU idle for seconds); it ramps the clock itself as well.
         scale = {}
-        if not args.no_anchor:
+        if args.full and not args.no_anchor:
             anchor = band_anchor(ctx, args, world, device, stream, (gb, outs) if banded and rgba8 else None)
             scale = {"scale_anchor": anchor}
             if world > 1:
@@ -738,7 +791,7 @@ def main():
         if world == 1 and args.mode == "faithful" and args.exact_leg:
             exact_leg = time_exact_mode(ctx, pc, gb, outs[0], stream, args, fmt, rgba8, band_px)
             exact_frame = outs[0][: band.rows].cpu().numpy()
-        if world == 1 and not args.no_cpu_baseline:
+        if want_cpu:
             cpu, parity, (step_, ref) = cpu_baseline(cfg, staging.numpy(), pc, env, frame, args.cpu_rows,
                                                     args.cpu_kind, rgba8)
             if exact_frame is not None:
@@ -748,7 +801,7 @@ def main():
                                                                rgba8)}
         out = {
             "metric": METRIC, "value": round(value, 2), "unit": "Mpix/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "clock_ramp": ramp,
+            "warmup": args.warmup, "full": args.full, "clock_ramp": ramp,
             "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "f32", "output": output, "mode": args.mode,
             "library": library,
@@ -769,6 +822,7 @@ def main():
             "cpu_baseline": cpu,
             **parity, **gather_note, **cull_note, **scale,
             **({"exact_mode": exact_leg} if exact_leg is not None else {}),
+            **({"dumped_outputs": dumped} if dumped is not None else {}),
             # pinned staging -> HBM: pcie_h2d_gbps = the copy repeated into the resident buffer (the
             # link rate; this key's meaning in round 4 and from round 6); pcie_h2d_first_gbps = the process's first
             # copy (device allocation + first DMA use of the pinned pages). Line schema 6 (line_schema).

@@ -215,6 +215,33 @@ def test_bench_refuses_to_publish_a_wrong_frame(capsys):
     assert json.loads(capsys.readouterr().out)["parity_checked"] is False
 
 
+def test_dump_outputs_writes_float32_within_the_budget(tmp_path, monkeypatch):
+    """--dump-outputs: a small output is written whole in its own shape, RGBA8 codes as float32 values; an output
+    over its share of the budget as the same seeded pixel sample on every call, so two builds can be compared."""
+    import torch
+
+    assert bench.DUMP_BUDGET_BYTES + 2 * 4096 <= 64 * 1000 * 1000  # the files' headers included
+    small = torch.arange(6 * 5 * 4, dtype=torch.float32).reshape(6, 5, 4)
+    small[2, 3, 1] = float("nan")
+    codes = (torch.arange(3 * 7 * 4) % 256).to(torch.uint8).reshape(3, 7, 4)
+    shapes = bench.dump_outputs(str(tmp_path / "a"), {"frame": small, "gathered_frame": codes})
+    assert shapes == {"frame": [6, 5, 4], "gathered_frame": [3, 7, 4]}
+    got = np.load(tmp_path / "a" / "frame.npy")
+    assert got.dtype == np.float32 and np.array_equal(got.view(np.uint32), small.numpy().view(np.uint32))
+    got8 = np.load(tmp_path / "a" / "gathered_frame.npy")
+    assert got8.dtype == np.float32 and np.array_equal(got8, codes.numpy().astype(np.float32))
+    # over the budget: 1000 pixels, room for 100 per file
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 2 * 100 * 16)
+    big = torch.arange(1000 * 4, dtype=torch.float32).reshape(25, 40, 4)
+    for d in ("b", "c"):
+        assert bench.dump_outputs(str(tmp_path / d), {"frame": big, "gathered_frame": codes}) == {
+            "frame": [100, 4], "gathered_frame": [3, 7, 4]}
+    b, c = np.load(tmp_path / "b" / "frame.npy"), np.load(tmp_path / "c" / "frame.npy")
+    assert np.array_equal(b, c) and b.nbytes + got8.nbytes <= bench.DUMP_BUDGET_BYTES
+    px = (b[:, 0] // 4).astype(int)  # channel 0 of pixel k is 4k: the sampled pixels, ascending and distinct
+    assert np.all(np.diff(px) > 0) and np.array_equal(b, big.reshape(-1, 4).numpy()[px])
+
+
 def test_scale_anchor_ramps_the_clock_before_timing(monkeypatch):
     """band_anchor runs the same untimed clock ramp as the headline (--ramp-ms) before its warm-up and timed
     steps, and reports it; the anchor is then comparable with the ramped per-N values it divides."""

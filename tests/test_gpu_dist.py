@@ -86,11 +86,11 @@ def test_eight_ranks_on_one_gpu_equal_single_frame(gpu):
 
 
 def test_bench_multi_rank_rehearsal(gpu):
-    """bench.py at N = 4 (gloo, the one GPU shared): one JSON line from rank 0 with the gathered bands'
+    """bench.py --full at N = 4 (gloo, the one GPU shared): one JSON line from rank 0 with the gathered bands'
     checksums matching and the per-rank band geometry of config 5."""
     cmd = TORCHRUN + ["--nproc-per-node", "4", os.path.join(ROOT, "bench.py"),
            "--gpus", "4", "--steps", "3", "--warmup", "1", "--ramp-ms", "0", "--dist-backend", "gloo",
-           "--rows-per-rank", "64"]
+           "--rows-per-rank", "64", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT,
                        env={**os.environ, "OMP_NUM_THREADS": "2"})
     assert r.returncode == 0, r.stderr[-3000:]
@@ -116,7 +116,7 @@ def test_bench_multi_rank_rehearsal(gpu):
 
 def _bench_torchrun(nproc, extra, timeout=600):
     cmd = TORCHRUN + ["--nproc-per-node", str(nproc), os.path.join(ROOT, "bench.py"),
-           "--gpus", str(nproc), "--steps", "3", "--warmup", "1", "--ramp-ms", "0"] + extra
+           "--gpus", str(nproc), "--steps", "3", "--warmup", "1", "--ramp-ms", "0", "--full"] + extra
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, cwd=ROOT,
                        env={**os.environ, "OMP_NUM_THREADS": "2"})
     assert r.returncode == 0, r.stderr[-3000:]
@@ -145,10 +145,10 @@ def test_bench_rccl_single_rank(gpu):
 
 
 def test_bench_config5_one_gpu_is_the_per_rank_workload(gpu):
-    """`bench.py --gpus 1 --config 5`: the same 8192 x 1024 band and RGBA8 output each rank of the N = 8 run
+    """`bench.py --gpus 1 --config 5 --full`: the same 8192 x 1024 band and RGBA8 output each rank of the N = 8 run
     shades (so the 1 -> 8 curve compares equal work), with the CPU leg on a row sample of that band."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "5", "--steps",
-                        "3", "--warmup", "1", "--ramp-ms", "0", "--cpu-rows", "16", "--cpu-kind", "port"],
+                        "3", "--warmup", "1", "--ramp-ms", "0", "--full", "--cpu-rows", "16", "--cpu-kind", "port"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
@@ -158,11 +158,11 @@ def test_bench_config5_one_gpu_is_the_per_rank_workload(gpu):
 
 
 def test_bench_default_line_carries_anchor_and_executed_roofline(gpu):
-    """`bench.py --gpus 1` (config 3): the line carries the scaling anchor -- one rank's config-5 band of
+    """`bench.py --gpus 1 --full` (config 3): the line carries the scaling anchor -- one rank's config-5 band of
     --rows-per-rank rows, RGBA8, the same mode -- and both roofline fractions, the executed one counting only
     the terms the pass evaluated (the wave-balanced lists skip back-facing ones)."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup",
-                        "1", "--ramp-ms", "0", "--no-cpu-baseline", "--rows-per-rank", "64"],
+                        "1", "--ramp-ms", "0", "--full", "--no-cpu-baseline", "--rows-per-rank", "64"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
@@ -188,7 +188,7 @@ def test_bench_exits_nonzero_on_a_parity_breach(gpu):
     import bench
 
     base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "1", "--steps", "3",
-            "--warmup", "1", "--ramp-ms", "0", "--no-anchor", "--cpu-kind", "port"]
+            "--warmup", "1", "--ramp-ms", "0", "--full", "--no-anchor", "--cpu-kind", "port"]
     r = subprocess.run(base + ["--inject-parity-breach", "2e-5"], capture_output=True, text=True, timeout=600,
                        cwd=ROOT)
     assert r.returncode == bench.EXIT_PARITY, r.stderr[-3000:]
@@ -197,3 +197,30 @@ def test_bench_exits_nonzero_on_a_parity_breach(gpu):
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
     assert d["parity_ok"] is True and d["parity_checked"] is True and d["parity_max_rel"] <= 1e-5
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_timed_frame(gpu, tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full runs no leg beside the headline (no CPU baseline, no
+    parity check, no scaling anchor) and --dump-outputs writes the frame its last timed step shaded: float32, and
+    bit for bit the frame the same pass gives when shaded here on the same deterministic G-buffer."""
+    from physically_based_renderer_amd import _native as N
+    from physically_based_renderer_amd import scenes as S
+    from physically_based_renderer_amd.renderer import ShadingContext
+
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "1", "--steps", "2",
+                        "--warmup", "1", "--ramp-ms", "0", "--dump-outputs", str(tmp_path / "out")],
+                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    assert d["full"] is False and d["steps"] == 2 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert d["cpu_baseline"] is None and d["parity_checked"] is False and "scale_anchor" not in d
+    assert d["dumped_outputs"] == {"frame": [256, 256, 4]} and os.listdir(tmp_path / "out") == ["frame.npy"]
+    got = np.load(tmp_path / "out" / "frame.npy")
+    assert got.dtype == np.float32 and got.shape == (256, 256, 4)
+    cfg = S.CONFIGS[1]
+    pc = S.scene_pass(cfg)
+    pc.flags = int(pc.flags) | N.PBR_FLAG_FAITHFUL  # the bench's default mode
+    with ShadingContext(0) as sc:
+        sc.set_pass(pc)
+        want = sc.shade(S.build_gbuffer(cfg, gpu)).cpu().numpy()
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))

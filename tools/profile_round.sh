@@ -1,6 +1,6 @@
 #!/bin/bash
 # Collect the round's rocprofv3 evidence on the gpurun box:
-#   1. --kernel-trace --stats of the default bench command (the bench line's own run);
+#   1. --kernel-trace --stats of the bench command with every leg (bench.py --full: the line with its parity check);
 #   2. separate --pmc passes (never combined with other traces): FETCH_SIZE, WRITE_SIZE, SQ
 #      instruction / cycle counters, on a short bench run of the same workload.
 # Output: gpurun_out/prof_<tag>/...; tools/pmc_summarize.py turns it into profiles/.
@@ -20,7 +20,7 @@ run() {  # name, timeout, command...
   tail -n 3 "$out/$name.log"
   return $rc
 }
-run kt 300 rocprofv3 --kernel-trace --stats -d "$out/kt" -o kt --output-format csv -- python3 bench.py "$@" &&
+run kt 300 rocprofv3 --kernel-trace --stats -d "$out/kt" -o kt --output-format csv -- python3 bench.py --full "$@" &&
 run pmc_fetch 300 rocprofv3 --pmc FETCH_SIZE -d "$out/pmc_fetch" -o pmc --output-format csv -- python3 bench.py --steps 5 --warmup 1 --ramp-ms 0 --no-cpu-baseline "$@" &&
 run pmc_write 300 rocprofv3 --pmc WRITE_SIZE -d "$out/pmc_write" -o pmc --output-format csv -- python3 bench.py --steps 5 --warmup 1 --ramp-ms 0 --no-cpu-baseline "$@" &&
 run pmc_sq 300 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS -d "$out/pmc_sq" -o pmc --output-format csv -- python3 bench.py --steps 5 --warmup 1 --ramp-ms 0 --no-cpu-baseline "$@" &&
