@@ -97,34 +97,57 @@ __device__ __forceinline__ bool zero_or_in(float x, float lo, float hi) { return
 #define PBR_POW5_LDS 1
 #endif
 #if PBR_POW5_LDS
-// The three tables back to back, 37 chunks of 16 bytes: powf's log2 rows (16 x 16 B), its exp2 words (32 x 8 B),
-// atanf's reduction rows (5 x 16 B). load_libm_tables copies them with one 16-byte load per work-item and a single
-// wait (three separately predicated copies each waited for their own load: three round trips before a wave's
-// G-buffer loads could issue).
+// The tables in 16-byte chunks: powf's log2 rows (16 x 16 B) and its exp2 words (32 x 8 B), 32 chunks, and atanf's
+// reduction rows laid out by key (81 x 16 B, libm_f32_x2.h), back to back in constant memory. load_libm_tables copies
+// them to LDS with one 16-byte load per work-item and a single wait (three separately predicated copies each waited
+// for their own load: three round trips before a wave's G-buffer loads could issue); a 64-lane workgroup that needs
+// the atan rows issues a second load in its first 49 lanes before that wait. The atan rows are an LDS variable of
+// their own, so that only the kernels that read them (diffuse-IBL ambient) allocate them.
 struct alignas(16) LibmTables {
     pbr_powf_log2_entry log2[16];
     uint64_t exp2[32];
-    pbr_atan_seg atan[5];  // libm_f32_x2.h
 };
-static_assert(sizeof(LibmTables) == 37 * 16, "one 16-byte chunk per work-item");
+struct alignas(16) LibmTablesAll {
+    LibmTables pow;
+    pbr_atan_seg atan[PBR_ATAN_KEYS];  // libm_f32_x2.h: row `key`
+};
+constexpr int kLibmPowChunks = sizeof(LibmTables) / 16, kLibmAllChunks = sizeof(LibmTablesAll) / 16;
+static_assert(kLibmPowChunks == 32 && kLibmAllChunks == 113, "16-byte chunks");
 __shared__ LibmTables g_lds_libm;
-static __constant__ LibmTables pbr_libm_tables = {PBR_POWF_LOG2_TABLE_INIT, PBR_EXP2F_TABLE_INIT,
-                                                  PBR_ATAN_SEG_TABLE_INIT};
+__shared__ pbr_atan_seg g_lds_atan[PBR_ATAN_KEYS];
+static __constant__ LibmTablesAll pbr_libm_tables = {{PBR_POWF_LOG2_TABLE_INIT, PBR_EXP2F_TABLE_INIT},
+                                                     PBR_ATAN_SEG_KEYED_INIT};
 // Every work-item of the block calls this, and a barrier follows before the first table read. ATAN: the kernel
-// evaluates the packed WorldToSkyUV (diffuse-IBL ambient); otherwise the atan rows are not copied.
-template <bool ATAN = true>
+// evaluates the packed WorldToSkyUV (diffuse-IBL ambient); otherwise the atan rows are not copied. THREADS: the
+// workgroup's size (64 or more).
+template <bool ATAN = true, int THREADS = 256>
 __device__ __forceinline__ void load_libm_tables() {
-    constexpr int kChunks = ATAN ? 37 : 32;
+    constexpr int kChunks = ATAN ? kLibmAllChunks : kLibmPowChunks;
+    static_assert(THREADS >= 64 && kChunks <= 2 * THREADS, "at most two chunks per work-item");
     const int t = threadIdx.x;
-    if (t < kChunks) reinterpret_cast<uint4*>(&g_lds_libm)[t] = reinterpret_cast<const uint4*>(&pbr_libm_tables)[t];
+    const uint4* src = reinterpret_cast<const uint4*>(&pbr_libm_tables);
+    auto dst = [](int c) -> uint4* {  // chunk c's place in LDS
+        if constexpr (ATAN) {
+            if (c >= kLibmPowChunks) return reinterpret_cast<uint4*>(g_lds_atan) + (c - kLibmPowChunks);
+        }
+        return reinterpret_cast<uint4*>(&g_lds_libm) + c;
+    };
+    if constexpr (kChunks <= THREADS) {
+        if (t < kChunks) *dst(t) = src[t];
+    } else {
+        const bool second = t + THREADS < kChunks;
+        const uint4 c0 = src[t], c1 = src[second ? t + THREADS : t];  // both loads in flight, one wait
+        *dst(t) = c0;
+        if (second) *dst(t + THREADS) = c1;
+    }
 }
 #define PBR_POW5_TABLES g_lds_libm.log2, g_lds_libm.exp2
 #define PBR_LIBM_LOG2_TAB g_lds_libm.log2
 #define PBR_LIBM_EXP2_TAB g_lds_libm.exp2
-#define PBR_LIBM_ATAN_TAB g_lds_libm.atan
+#define PBR_LIBM_ATAN_TAB g_lds_atan
 #else
-static __constant__ pbr_atan_seg pbr_atan_seg_tab[5] = PBR_ATAN_SEG_TABLE_INIT;
-template <bool ATAN = true>
+static __constant__ pbr_atan_seg pbr_atan_seg_tab[PBR_ATAN_KEYS] = PBR_ATAN_SEG_KEYED_INIT;
+template <bool ATAN = true, int THREADS = 256>
 __device__ __forceinline__ void load_libm_tables() {}
 #define PBR_POW5_TABLES pbr_powf_log2_tab, pbr_exp2f_tab
 #define PBR_LIBM_LOG2_TAB pbr_powf_log2_tab
@@ -389,19 +412,50 @@ __device__ __forceinline__ int wrap_index(float f, int n) {
     return m < 0 ? m + n : m;
 }
 
+// The texel wrap for the (u, v) WorldToSkyUV gives an element that is not `special` (atan2f and asinf returned
+// finite values of their ranges). WorldToSkyUV's own operations bound the coordinates, every step being monotonic
+// under round-to-nearest, so that the bounds of the exact expressions carry over at values fp32 represents:
+//   |atan2f| <= 3.1415927410 (fp32 pi); * 0.1591 -> |.| <= 0.49983 < 0.5; + 0.5 -> [1.7e-4, 0.99983]; 1 - . -> the
+//   same interval; + 0.25 -> u in [0.25, 1.25];
+//   |asinf| <= 1.5707963705; * 0.3183 -> |.| <= 0.4999845; + 0.5 -> [1.5e-5, 0.9999845]; 1 - . -> v in (0, 1).
+// With x = u w - 0.5 and y = v h - 0.5 (w, h >= 1; RN(u w) <= RN(1.25 w), and 1.25 w - 0.5 is below 2 w by at
+// least 1.25, far more than the roundings of numbers below 2^31 move it):
+//   x in [0.25 w - 0.5, 1.25 w - 0.5]: floor(x) in [-1, 2 w);     y in (-0.5, h - 0.5): floor(y) in [-1, h).
+// So the column needs at most one added w (only for -1) or one subtracted w, and the row at most one added h.
+// Exactly one of i + w, i, i - w lies in [0, w); read as unsigned numbers the other two are at least w (a negative
+// one wraps to >= 2^31), so the unsigned minimum picks it: no compare, no select, no branch. Env maps hold at most
+// 2^26 texels (set_texture, pbr_context.hip), so nothing overflows. An element outside the bounds (a special one)
+// must not come here: the result would index outside the map.
+__device__ __forceinline__ int wrap_sky_column(float f, int w) {
+    const uint32_t i = (uint32_t)(int)f, n = (uint32_t)w;
+    return (int)min(min(i + n, i), i - n);
+}
+__device__ __forceinline__ int wrap_sky_row(float f, int h) {
+    const uint32_t i = (uint32_t)(int)f;
+    return (int)min(i + (uint32_t)h, i);
+}
+
 // Linear-wrap bilinear sample (g_SamLinearWrap, PBRApp.cpp:1157-1162) of the fp32 RGBA env map
-// (texels pre-decoded as u16 / 65535.0f), in the fp32 formula fixed by DESIGN.md.
+// (texels pre-decoded as u16 / 65535.0f), in the fp32 formula fixed by DESIGN.md. SKY_BOUNDED: (u, v) are
+// WorldToSkyUV's for a non-special element (wrap_sky_column / wrap_sky_row); otherwise any value (wrap_index).
+template <bool SKY_BOUNDED = false>
 __device__ __forceinline__ f3 sample_linear_wrap(const float4* __restrict__ env, int w, int h, float u, float v) {
     float x = u * (float)w - 0.5f;
     float y = v * (float)h - 0.5f;
     float x0f = floorf(x), y0f = floorf(y);
     float fx = x - x0f, fy = y - y0f;
-    int x0 = wrap_index(x0f, w), y0 = wrap_index(y0f, h);
+    int x0 = SKY_BOUNDED ? wrap_sky_column(x0f, w) : wrap_index(x0f, w);
+    int y0 = SKY_BOUNDED ? wrap_sky_row(y0f, h) : wrap_index(y0f, h);
     int x1 = x0 + 1 == w ? 0 : x0 + 1;
     int y1 = y0 + 1 == h ? 0 : y0 + 1;
     [[maybe_unused]] const int64_t n = (int64_t)w * h;
-    float4 t00 = env[PBR_BOUNDS(y0 * w + x0, n, kBoundsTexel)], t10 = env[PBR_BOUNDS(y0 * w + x1, n, kBoundsTexel)];
-    float4 t01 = env[PBR_BOUNDS(y1 * w + x0, n, kBoundsTexel)], t11 = env[PBR_BOUNDS(y1 * w + x1, n, kBoundsTexel)];
+    // Texel addresses as unsigned 32-bit byte offsets on the (uniform) base pointer: a map holds at most 2^26 texels
+    // (set_texture, pbr_context.hip), 2^30 bytes, so the offset needs no 64-bit arithmetic per lane.
+    auto texel = [&](int ty, int tx) {
+        const uint32_t off = (uint32_t)PBR_BOUNDS(ty * w + tx, n, kBoundsTexel) * (uint32_t)sizeof(float4);
+        return *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(env) + off);
+    };
+    const float4 t00 = texel(y0, x0), t10 = texel(y0, x1), t01 = texel(y1, x0), t11 = texel(y1, x1);
     return mk3(hlerp(hlerp(t00.x, t10.x, fx), hlerp(t01.x, t11.x, fx), fy),
                hlerp(hlerp(t00.y, t10.y, fx), hlerp(t01.y, t11.y, fx), fy),
                hlerp(hlerp(t00.z, t10.z, fx), hlerp(t01.z, t11.z, fx), fy));

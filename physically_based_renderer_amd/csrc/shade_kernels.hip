@@ -584,21 +584,40 @@ __device__ __forceinline__ f3x2 ambient_ibl_pair(const PixelInvariants2& q, cons
     const f3x2 kd = f3x2{(1.0f - (q.f0.x + q.one_minus_f0.x * pw)) * q.one_minus_metal,
                          (1.0f - (q.f0.y + q.one_minus_f0.y * pw)) * q.one_minus_metal,
                          (1.0f - (q.f0.z + q.one_minus_f0.z * pw)) * q.one_minus_metal};
-    // WorldToSkyUV (LightingUtil.hlsl:216-225)
-    int sa[2], sb[2];
-    v2 ux = pbr_atan2f_x2(q.n.z, q.n.x, sa, PBR_LIBM_ATAN_TAB);
-    v2 uy = pbr_asinf_x2(q.n.y, sb);
-    const bool spec_a = live_a && (sa[0] | sb[0]), spec_b = live_b && (sa[1] | sb[1]);
-    if (__builtin_expect(lanes(spec_a || spec_b) != 0, 0)) {
-        PBR_COLD("ibl_special");
-        if (spec_a) {
-            ux.x = pbr_atan2f(q.n.z.x, q.n.x.x);
-            uy.x = pbr_asinf(q.n.y.x);
+    // WorldToSkyUV (LightingUtil.hlsl:216-225): the main parts of the pair forms for every element; their patches
+    // (a zero component, the exponent-gap shortcuts, |N.y| == 1) in one wave-uniform branch, only when an element
+    // of the wave is odd; the scalar functions inside it for live special elements (libm_f32_x2.h).
+    // `odd` is not masked by `live`: an element that is not live may hold anything, and only an element that is not
+    // special has the bounded texel coordinates the branch-free wrap needs (pbr_device_math.h, wrap_sky_column), so
+    // a wave with any special element, live or not, takes the general wrap.
+    int oa[2], ob[2];
+    v2 q_abs;
+    const v2 az = pbr_atan2f_x2_head(q.n.z, q.n.x, oa, &q_abs, PBR_LIBM_ATAN_TAB, 1);
+    v2 uy = pbr_asinf_x2_main(q.n.y, ob);
+    v2 ux;
+    bool any_special = false;  // wave-uniform
+    if (__builtin_expect(lanes((oa[0] | ob[0] | oa[1] | ob[1]) != 0) != 0, 0)) {
+        PBR_COLD("ibl_patch");
+        int sa[2], sb[2];
+        ux = pbr_atan2f_x2_tail_patch(q.n.z, q.n.x, q_abs, az);
+        uy = pbr_asinf_x2_patch(q.n.y, uy, sb);
+        pbr_atan2f_x2_special(q.n.z, q.n.x, sa);
+        const bool sp_a = (sa[0] | sb[0]) != 0, sp_b = (sa[1] | sb[1]) != 0;
+        any_special = lanes(sp_a || sp_b) != 0;
+        const bool spec_a = live_a && sp_a, spec_b = live_b && sp_b;
+        if (__builtin_expect(lanes(spec_a || spec_b) != 0, 0)) {
+            PBR_COLD("ibl_special");
+            if (spec_a) {
+                ux.x = pbr_atan2f(q.n.z.x, q.n.x.x);
+                uy.x = pbr_asinf(q.n.y.x);
+            }
+            if (spec_b) {
+                ux.y = pbr_atan2f(q.n.z.y, q.n.x.y);
+                uy.y = pbr_asinf(q.n.y.y);
+            }
         }
-        if (spec_b) {
-            ux.y = pbr_atan2f(q.n.z.y, q.n.x.y);
-            uy.y = pbr_asinf(q.n.y.y);
-        }
+    } else {
+        ux = pbr_atan2f_x2_tail(q.n.z, q.n.x, az);
     }
     ux = ux * 0.1591f;
     uy = uy * 0.3183f;
@@ -607,8 +626,15 @@ __device__ __forceinline__ f3x2 ambient_ibl_pair(const PixelInvariants2& q, cons
     uy = 1.0f - uy;
     ux = 1.0f - ux;
     ux = ux + 0.25f;
-    const f3 ia = sample_linear_wrap(env, ps.env_w, ps.env_h, ux.x, uy.x);
-    const f3 ib = sample_linear_wrap(env, ps.env_w, ps.env_h, ux.y, uy.y);
+    f3 ia, ib;
+    if (__builtin_expect(any_special, 0)) {
+        PBR_COLD("ibl_wrap_general");
+        ia = sample_linear_wrap(env, ps.env_w, ps.env_h, ux.x, uy.x);
+        ib = sample_linear_wrap(env, ps.env_w, ps.env_h, ux.y, uy.y);
+    } else {
+        ia = sample_linear_wrap<true>(env, ps.env_w, ps.env_h, ux.x, uy.x);
+        ib = sample_linear_wrap<true>(env, ps.env_w, ps.env_h, ux.y, uy.y);
+    }
     const f3x2 irr = f3x2{v2{ia.x, ib.x}, v2{ia.y, ib.y}, v2{ia.z, ib.z}};
     return f3x2{kd.x * (irr.x * q.albedo.x), kd.y * (irr.y * q.albedo.y), kd.z * (irr.z * q.albedo.z)};
 }
@@ -875,7 +901,7 @@ __global__ __launch_bounds__(BAL != 0 && PBR_BAL_WAVES == 1 ? 64 : kBlock, PBR_X
     unsigned long long* bal_prof = s.prof[__builtin_amdgcn_readfirstlane(threadIdx.x) >> 6];
     if ((threadIdx.x & 63) < 16) bal_prof[threadIdx.x & 63] = 0;
 #endif
-    load_libm_tables<AMBIENT == kAmbientIblDiffuse>();  // powf (+ atanf with IBL) tables -> LDS (pbr_device_math.h)
+    load_libm_tables<AMBIENT == kAmbientIblDiffuse, (BAL != 0 && PBR_BAL_WAVES == 1 ? 64 : kBlock)>();  // powf (+ atanf with IBL) tables -> LDS
     if constexpr (BAL != 0)
         stage_balanced_lights<kOneWave ? 64 : kBlock>(lights, ps.n_dir, ps.n_dir + ps.n_point, s.bal_light,
                                                       BAL == 2 ? 4.0f : 1.0f);
@@ -1367,7 +1393,7 @@ __global__ __launch_bounds__(64, (lean_min_waves<AMBIENT, CULL, FAITHFUL>())) vo
                                                             const float4* __restrict__ env, FrameArgs fr,
                                                             int32_t* __restrict__ tile_kept) {
     // powf tables -> LDS: the exact finish's gamma, spot cones, the faithful gamma's edges (+ atanf rows with IBL)
-    load_libm_tables<AMBIENT == kAmbientIblDiffuse>();
+    load_libm_tables<AMBIENT == kAmbientIblDiffuse, 64>();
     __syncthreads();
 #if PBR_LEAN_TILES == 2
     // Development (PBR_LEAN_TILES=2, uniform loops): each wave shades two tiles' 64x2 pixels, tile rows 2t and 2t + 1
@@ -1464,7 +1490,7 @@ __global__ __launch_bounds__(kBlock) void shade_tile1_kernel(GBufferArgs gb, Pas
                                                              int32_t* __restrict__ tile_kept,
                                                              bool exact_only) {
     __shared__ Lds s;
-    load_libm_tables<AMBIENT == kAmbientIblDiffuse>();  // powf (+ atanf with IBL) tables -> LDS (pbr_device_math.h)
+    load_libm_tables<AMBIENT == kAmbientIblDiffuse, kBlock>();  // powf (+ atanf with IBL) tables -> LDS (pbr_device_math.h)
     __syncthreads();
     const int tid = threadIdx.x;
     const int x = blockIdx.x * kTileW1 + (tid & (kTileW1 - 1));
