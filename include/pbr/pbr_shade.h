@@ -89,9 +89,12 @@ enum pbr_pass_flags {
                                          6.4e-6; measured 6.3e-7), not bit-identical.
                                          Applies where every light term is >= 0 and the sum is short:
                                          <= 64 lights (with PBR_FLAG_TILED_CULLING: <= 64 surviving lights,
-                                         counted per wave), non-negative strengths, ambient and env texels
-                                         (checked on the host), albedo >= 0 and F0 in [0, 1] (checked per
-                                         wave); elsewhere the pass stays exact. */
+                                         counted per wave), every strength component of every light 0 or in
+                                         [2^-25, 2^50] (outside it a product of the rearranged term underflows
+                                         or the reference's own overflows to NaN), a constant ambient and
+                                         env texels in [0, 2^100] (checked on the host), albedo
+                                         >= 0 and F0 in [0, 1] (checked per wave); elsewhere the pass stays
+                                         exact. */
     PBR_FLAG_ALPHA_TEST = 1u << 5     /* ABI 6: the ALPHA_TEST permutation (alphaTestedPS, PBRApp.cpp:750-765,
                                          Default.hlsl:111-113): fragOpacity = the G-buffer's opacity plane;
                                          a pixel with fragOpacity - 0.1f < 0 is discarded (its output is left

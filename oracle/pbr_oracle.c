@@ -50,7 +50,16 @@ static inline float calc_attenuation(float d) {
 /* FresnelSchlick, LightingUtil.hlsl:43-47 */
 static inline v3 fresnel_schlick(v3 h, v3 v, v3 f0) {
     float cos_theta = hsat(dot3(h, v));
+#ifdef ORACLE_POW5_FP64
+    /* Test variant (Makefile, POW5_OUT): the kernels' x^5 -- the correctly rounded fp64 products below 0.99, powf in
+     * the grazing band (csrc/pbr_device_math.h, pow5_light) -- to tell the exact mode's documented 1-ulp residue from
+     * any other difference (tests/test_strength_range_cases.py). */
+    float x = 1.0f - cos_theta;
+    double dx2 = (double)x * (double)x;
+    float p = x > 0.99f ? powf(x, 5.0f) : (float)(dx2 * dx2 * (double)x);
+#else
     float p = powf(1.0f - cos_theta, 5.0f);
+#endif
     return v3make(f0.x + (1.0f - f0.x) * p, f0.y + (1.0f - f0.y) * p, f0.z + (1.0f - f0.z) * p);
 }
 

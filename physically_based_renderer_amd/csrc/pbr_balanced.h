@@ -35,7 +35,10 @@
 // max(dot(N, H), 0) and saturate(dot(H, V)) map NaN to 0 (IEEE maxNum, LightingUtil.hlsl:55, 45), so NDF and
 // F stay finite and G = 0. The pixel on the light (l = 0: L = 0 / 0 = NaN) is the same case. Every other
 // factor is finite for a pixel and light inside the fast-path window (the lean-wave bounds of brdf_x2: den in
-// [2^-37, PI], F0 window; attenuation <= 1e4). So every skipped term is +-0 in the reference and needs no
+// [2^-37, PI], F0 window; attenuation <= 1e4) once the radiance s att is: the host runs the balanced lists only
+// for strengths within 2^50 (pbr_context.hip: kQuarterStrengthHi for exact passes, kFaithfulStrengthHi for
+// faithful ones), so s att <= 2^63.3, where a larger strength next to the light overflows and the reference's
+// back-faced term is inf * 0 = NaN. So every skipped term is +-0 in the reference and needs no
 // window test; live items run the |V + L| >= 2^-30 test in pass 2, and their distance window (a light closer than
 // 0.01, 2^-20 in exact mode) is decided in pass 1 (balanced_pass1: near_a / near_b), so either sends the pixel to the
 // exact re-pass as the plain loop would, here only when the item is live. Lights whose fast-path flag is off (pbr_set_pass) make the host choose the uniform loop
@@ -83,7 +86,8 @@ __device__ unsigned long long* g_bal_prof_buf;  // 16 per wave, wave = block * 4
 constexpr int kBalLdsStride = kBalMaxLights + 4;  // 68 floats: every array 16-byte aligned
 constexpr float kBalSentinelPos = 0x1p24f;
 // `strength_scale`: 4 for the exact balanced kernel, whose items take 4x the radiance (brdf_x2's QUARTER form; the host
-// keeps every point strength within 2^50 for it, so the product cannot overflow), 1 otherwise. NT: the
+// keeps every point strength 0 or within [2^-34, 2^50] for it, pbr_context.hip kQuarterStrengthLo / Hi, so the product
+// neither overflows nor leaves a subnormal product behind that the unscaled loop rounds differently), 1 otherwise. NT: the
 // workgroup's work-items (64 in one-wave workgroups: two rounds for the 68 entries).
 template <int NT = 256>
 __device__ __forceinline__ void stage_balanced_lights(const float4* __restrict__ lights, int b0, int b1,
@@ -385,6 +389,8 @@ __device__ __forceinline__ void read_pair_lights(const float* lds_lights, int j0
 // within ~3.6 degrees of -V: rare, as the glibc band is) does the wave run the window test and the band patch, as a
 // uniform branch: 2 compares per iteration instead of 4.
 constexpr float kBalNearVL = 0.0625f;
+static_assert(PBR_POW5_FAST3_GLIBC_FROM >= 1.0f - 0.5f * kBalNearVL + 0x1p-14f,
+              "a |V + L| >= kBalNearVL item has x < 0.9688: pow5_fast3's glibc band (a build switch) must start above it");
 __device__ __forceinline__ void faithful_point_items2(const ItemPixel& q, const f3x2& lp, const f3x2& ls, m2& ok,
                                                       f3x2& sum, uint64_t live) {
     f3x2 l = f3x2{lp.x - q.pos.x, lp.y - q.pos.y, lp.z - q.pos.z};

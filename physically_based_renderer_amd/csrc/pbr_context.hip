@@ -26,6 +26,68 @@ __attribute__((used)) const char pbr_unit_info_pbr_context[] =
     PBR_UNIT_INFO("pbr_context", PBR_BI_SWITCH(PBR_DEBUG_BOUNDS));
 }
 
+namespace {
+
+// ---- Strength and ambient gates of pbr_set_pass -------------------------------------------------------------------
+// The rescaled and reordered forms of the light term are the reference's only while no intermediate is subnormal, or
+// overflows, where the reference's own is not. The factor bounds used below are the project's (pbr_device_math.h,
+// fast_window_ok; pbr_device_math_x2.h, brdf_x2): an in-range point light's attenuation 1 / max(d, 0.01)^2 lies in
+// [1e-4, 1e4] = [2^-13.3, 2^13.3] (beyond the range it is exactly 0); in a lean wave the per-channel factor
+// Y = kD albedo / PI + spec of a term has kD albedo 0 or >= 2^-68 and spec = NDF G F / (4 N.V N.L + 0.001) 0 or
+// >= 2^-30 x 2^-45 / 2^2.01 (the NDF G window, the F bound, the denominator's maximum), so with albedo >= 0 and F0 <= 1 (kD albedo >= 0:
+// no cancellation) Y is 0 or >= 2^-78, and Y <= 2^57.1; N.L / 4 is 0 or >= 2^-110.
+//
+// The exact wave-balanced items (brdf_x2's QUARTER form, pbr_balanced.h) stage 4 s and evaluate
+// (Y (4 s att)) (N.L / 4) for the reference's (Y (s att)) N.L. The last product rounds the same real number either
+// way once its operands are exact multiples of four of one another, so the two forms differ only where 4 s, s att or
+// Y (s att) is not scaled exactly:
+//  * Hi: |s| <= 2^50 keeps Y 4 s att below 2^57.1 x 2^52 x 2^13.3 < 2^126: no overflow the reference does not have;
+//  * Lo: |s| >= 2^-34 keeps |s att| >= 2^-47.3 and |Y (s att)| >= 2^-78 x 2^-47.3 > 2^-126 wherever it is not 0: every
+//    product is normal in the reference's order, so its 4x is exact. (Found at 2^-115 and below by
+//    tests/test_gpu_strength_range.py: s att subnormal in the reference, normal in the 4x form.)
+//    NOT covered (residues): the pixel window admits albedo and F0 components of either sign up to 1024.
+//    A negative albedo channel, or F0 > 1 (albedo > 1 on a metal: kD < 0), gives kD albedo / PI the sign opposite to
+//    spec, and Y may cancel down to one ulp of its operands, 2^-101. Covering that takes |s| >= 2^-11.7 (Y (s att) >=
+//    2^-101 x 2^-25), which would take every pass with a strength below 5e-4 off the balanced kernel; the gate stays at
+//    2^-34, and for such a pixel the bit-identity of strengths in [2^-34, 2^-11.7) is not proved.
+// Passes outside the gate run the uniform exact loop.
+constexpr float kQuarterStrengthLo = 0x1p-34f, kQuarterStrengthHi = 0x1p50f;
+
+// PBR_FLAG_FAITHFUL forms X (s (att N.L / 4)) per term, skips back-faced items (pbr_balanced.h) and keeps a pixel
+// whose sum is 0 or inside [2^-100, 2^100] (shade_kernels.hip, the sum window). Every strength component of every
+// light kind must be 0 or inside [Lo, Hi]:
+//  * Hi = 2^50: X s att <= 2^57.1 x 2^50 x 2^13.3 stays finite, so the reference's (X (s att)) N.L is not NaN for a
+//    term with N.L = 0 (inf x 0), which the faithful loops evaluate as s x 0 = 0 or skip. (A strength of 3e38 half a
+//    unit behind a pixel made the reference's pixel NaN and the faithful one finite.)
+//  * Lo = 2^-25: s (att N.L / 4) >= 2^-25 x 2^-13.3 x 2^-110 > 2^-149 for every live term, so the product never
+//    underflows to 0 and a pixel the reference lights cannot come out with a kept sum of exactly 0 (with a
+//    subnormal strength and X in the hundreds it did). Where that product is subnormal, att N.L / 4 < 2^-101, so
+//    N.L < 2^-85 and the specular factor is below 2^30.1 N.L: X <= 2^10.4 is the diffuse factor alone, the term's
+//    absolute error is <= 2^10.4 x 2^-150, and 64 such terms move a kept sum (>= 2^-100) by less than 2^-33 of it.
+//    What remains is a term within the mode's relative error of the rounding boundary 2^-150 itself.
+//    The attenuation bound is the point lights' (a directional light's is 1). A SPOT light's att also carries the cone
+//    pow(c, SpotPower), which can be arbitrarily small: there the product can still underflow, or lose bits where the
+//    reference's s att is normal, whatever Lo is. The sum window redoes such a pixel unless the sum is kept (exactly 0, or
+//    lifted past 2^-100 by a strength near Hi): NOT covered by this gate (residues; not measured).
+constexpr float kFaithfulStrengthLo = 0x1p-25f, kFaithfulStrengthHi = 0x1p50f;
+
+// The faithful finish's Reinhard is c x v_rcp_f32(c + 1) (shade_kernels.hip, reinhard_faithful), and gfx950's v_rcp_f32
+// returns 0 where the reciprocal is subnormal (c + 1 >= 2^126: the output was 0 where the reference has ~1). The light
+// sum is within 2^100 (the sum window) and an in-window albedo within 2^10, so a constant ambient colour within 2^100
+// keeps c + 1 below 2^111. The IBL ambient is kD (irradiance albedo) with kD in [0, 1] in a faithful wave (F0 in [0, 1])
+// and the irradiance a convex combination of texels, so the same bound on every texel of an fp32 environment map does
+// the same (pbr_set_env_map tracks it beside the sign; UNORM16 texels are <= 1). (Out-of-window albedos already send
+// their pixels to the exact finish. The AO plane of PBR_FLAG_APPLY_AO multiplies the ambient term per pixel and is not
+// windowed: a value above 2^15 is outside this bound)
+constexpr float kFaithfulAmbientHi = 0x1p100f;
+
+inline bool zero_or_within(float x, float lo, float hi) {
+    const float a = std::fabs(x);
+    return a == 0.0f || (a >= lo && a <= hi);  // false for NaN
+}
+
+}  // namespace
+
 // Cross-stream ordering of the context's device resources (the reference's 3-deep FrameResource ring,
 // FrameResource.h:111-140, PBRApp.cpp:220-243, is the same idea on D3D12 fences). A resource -- a light slot,
 // the env map, the sky map -- remembers which streams have queued a pass reading it since it was last written
@@ -82,7 +144,7 @@ struct pbr_context {
         uint16_t* d_u16 = nullptr;  // UNORM16 upload staging
         float4* d = nullptr;
         int w = 0, h = 0, capacity = 0;
-        bool nonneg = true;  // no negative or NaN texel (PBR_FLAG_FAITHFUL precondition for the IBL)
+        bool faithful_ok = true;  // every texel in [0, kFaithfulAmbientHi], none NaN (PBR_FLAG_FAITHFUL precondition for the IBL)
         Resource use;
     };
     Texture env, sky;
@@ -91,7 +153,7 @@ struct pbr_context {
     int ambient_mode = 0;
     uint32_t flags = 0;
     bool pass_set = false;
-    bool faithful_pass_ok = false;  // light strengths and the constant ambient are finite and >= 0
+    bool faithful_pass_ok = false;  // light strengths and the constant ambient inside PBR_FLAG_FAITHFUL's windows (pbr_set_pass)
     bool faithful_count_terms = false;  // > 64 lights (culled pass): the kernel counts summed terms per wave
     int last_stream = -1;  // StreamState index of the context's last pass (pbr_last_pass_stats fallback)
     // Wave-balanced point-light lists (pbr_balanced.h) for untiled passes with at least this many point lights
@@ -99,7 +161,7 @@ struct pbr_context {
     // PBR_BALANCED_MIN overrides both (0 disables).
     int balanced_min = -1;
     bool points_flag_ok = false;  // pbr_set_pass: every point light inside the fast-path window
-    bool points_quarter_ok = false;  // ... and every point strength within 2^50 (the exact balanced items' 4x radiance)
+    bool points_quarter_ok = false;  // ... and every point strength inside the quarter gate (the exact balanced items' 4x radiance)
     int pixels_per_thread = 2;  // kernel layout: packed pixel pairs (measured faster); PBR_PIXELS_PER_THREAD=1 overrides
     bool lean = true;  // uniform-loop passes without a sky pass use the lean pair kernel (PBR_LEAN=0: off)
     std::string last_error;
@@ -408,10 +470,7 @@ int pbr_set_pass(pbr_context* ctx, const pbr_pass_desc* pass, void* stream) {
         sl.capacity = cap;
     }
     bool points_ok = true;  // every point light's fast-path flag is set (the balanced pass needs it)
-    // The exact balanced kernel's items carry 4x the radiance (pbr_balanced.h, stage_balanced_lights; brdf_x2's QUARTER
-    // form): with |strength| <= 2^50 the scaled products stay below 2^126 (term factors <= 2^57.1 x 2^13.3 attenuation
-    // x 4 x 2^50), so every scaling is exact and no term overflows where the reference's does not.
-    bool quarter_ok = true;
+    bool quarter_ok = true;  // ... and every point strength is inside the quarter gate (kQuarterStrengthLo / Hi)
     if (n > 0) {
         std::memcpy(sl.h, pass->lights, sizeof(pbr_light) * (size_t)n);
         // The kernel's per-light fast-path flag travels in the unused pad1 of the uploaded copy
@@ -434,7 +493,8 @@ int pbr_set_pass(pbr_context* ctx, const pbr_pass_desc* pass, void* stream) {
             L.pad1 = ok ? 1.0f : 0.0f;
             if (i >= nd && i < nd + np) {
                 points_ok = points_ok && ok;
-                for (int k = 0; k < 3; ++k) quarter_ok = quarter_ok && std::fabs(L.strength[k]) <= 0x1p50f;
+                for (int k = 0; k < 3; ++k)
+                    quarter_ok = quarter_ok && zero_or_within(L.strength[k], kQuarterStrengthLo, kQuarterStrengthHi);
             }
         }
         e = before_write(ctx, sl.use, s, si);
@@ -465,16 +525,21 @@ int pbr_set_pass(pbr_context* ctx, const pbr_pass_desc* pass, void* stream) {
     p.n_point = np;
     p.n_spot = ns;
     // PBR_FLAG_FAITHFUL's error bound needs every term of the light sum >= 0
-    // (pbr_device_math_x2.h, brdf_faithful_x2): finite non-negative strengths and a non-negative constant
-    // ambient; and at most 64 summed terms, since the sum's rounding drift grows by <= 1 ulp per term --
+    // (pbr_device_math_x2.h, brdf_faithful_x2): non-negative strengths inside the strength window
+    // (kFaithfulStrengthLo / Hi: NaN and infinities fail it) and a constant ambient in [0, kFaithfulAmbientHi];
+    // and at most 64 summed terms, since the sum's rounding drift grows by <= 1 ulp per term --
     // with tiled culling the kernel counts each wave's surviving lights (faithful mode 2).
     ctx->faithful_count_terms = n > 64;
-    bool nonneg = n <= 64 || (pass->flags & PBR_FLAG_TILED_CULLING) != 0;
+    bool faithful_ok = n <= 64 || (pass->flags & PBR_FLAG_TILED_CULLING) != 0;
     for (long long i = 0; i < n; ++i)
-        for (int k = 0; k < 3; ++k) nonneg = nonneg && std::isfinite(pass->lights[i].strength[k]) && pass->lights[i].strength[k] >= 0.0f;
+        for (int k = 0; k < 3; ++k) {
+            const float st = pass->lights[i].strength[k];
+            faithful_ok = faithful_ok && (st == 0.0f || (st >= kFaithfulStrengthLo && st <= kFaithfulStrengthHi));
+        }
     if (pass->ambient_mode == PBR_AMBIENT_CONSTANT)
-        for (int k = 0; k < 3; ++k) nonneg = nonneg && pass->ambient_light[k] >= 0.0f;
-    ctx->faithful_pass_ok = nonneg;
+        for (int k = 0; k < 3; ++k)
+            faithful_ok = faithful_ok && pass->ambient_light[k] >= 0.0f && pass->ambient_light[k] <= kFaithfulAmbientHi;
+    ctx->faithful_pass_ok = faithful_ok;
     ctx->points_flag_ok = points_ok;
     ctx->points_quarter_ok = points_ok && quarter_ok;
     ctx->ambient_mode = pass->ambient_mode;
@@ -531,10 +596,11 @@ int set_texture(pbr_context* ctx, pbr_context::Texture& t, const void* texels, b
     t.use.writer = -1;  // complete: later passes on any stream see the new texels
     t.w = width;
     t.h = height;
-    t.nonneg = true;
+    t.faithful_ok = true;  // UNORM16 texels are in [0, 1]
     if (!unorm16) {
         const float* f = static_cast<const float*>(texels);
-        for (size_t i = 0; i < 4 * (size_t)n && t.nonneg; ++i) t.nonneg = f[i] >= 0.0f;  // false for NaN
+        for (size_t i = 0; i < 4 * (size_t)n && t.faithful_ok; ++i)
+            t.faithful_ok = f[i] >= 0.0f && f[i] <= kFaithfulAmbientHi;  // false for NaN
     }
     return PBR_OK;
 }
@@ -602,7 +668,7 @@ int shade(pbr_context* ctx, const pbr_gbuffer_soa* gb, const pbr_frame_desc* fr,
     a.cull = cull;
     a.exact_only = (ctx->flags & PBR_FLAG_EXACT_ONLY) != 0;
     a.ps.faithful = (ctx->flags & PBR_FLAG_FAITHFUL) && !a.exact_only && ctx->faithful_pass_ok &&
-                    (ctx->ambient_mode != PBR_AMBIENT_IBL_DIFFUSE || ctx->env.nonneg);
+                    (ctx->ambient_mode != PBR_AMBIENT_IBL_DIFFUSE || ctx->env.faithful_ok);
     if (a.ps.faithful && ctx->faithful_count_terms) a.ps.faithful = 2;
     a.pixels_per_thread = ctx->pixels_per_thread;
     // Wave-balanced point-light lists: untiled pair-kernel passes with no spot lights, every point light inside

@@ -398,11 +398,12 @@ __device__ __forceinline__ v2 spot_range_select(v2 att, v2 dist) {
 }
 
 // ComputePointLight / ComputeSpotLight, packed fast path. The range test (exact, as in the scalar
-// version) scales the attenuation by 1 or 0 (in_range01), so an unlit lane's contribution is
-// (finite) * 0 = +-0 whenever the lane is inside the window (`ok`: every value of the fast path is then
-// finite; pbr_set_pass clears the light's window flag when its strength is not finite), and adding +-0
-// to the running sum is the identity the reference's skipped light is. Lanes outside the window are
-// redone by the caller whether lit or not.
+// version) scales the attenuation by 1 or 0 (in_range01), so an unlit lane's radiance is s * 0 = +-0
+// (pbr_set_pass clears the light's window flag when its strength is not finite) and its contribution
+// (finite) * 0 = +-0 whenever the lane is inside the window, and adding +-0 to the running sum is the
+// identity the reference's skipped light is. A lit lane's radiance s * att is formed in the reference's
+// order and may overflow with it (a strength above ~2^114 next to the light): a back-faced pixel's term is
+// then inf * 0 = NaN here as it is there. Lanes outside the window are redone by the caller whether lit or not.
 template <bool SPOT, bool LEAN>
 __device__ __forceinline__ f3x2 point_or_spot_x2(const PixelInvariants2& q, const f3x2& pos,
                                                  float4 s, float4 d, float4 p, m2& ok) {

@@ -544,7 +544,11 @@ __device__ __forceinline__ float reinhard(float c, bool fast) {
     return c / (c + 1.0f);
 }
 // PBR_FLAG_FAITHFUL waves: Reinhard with the hardware reciprocal (c >= 0 here; inf / NaN give NaN as
-// the IEEE quotient does) and the gamma encode of pow_inv_gamma_faithful.
+// the IEEE quotient does) and the gamma encode of pow_inv_gamma_faithful. v_rcp_f32 returns 0 where
+// the reciprocal is subnormal (c + 1 >= 2^126; measured on gfx950, tests/test_gpu_strength_range.py on the parent of
+// the gate), which would make the pixel 0 where the quotient is ~1: the sum window (<= 2^100) and the host's bound on
+// the constant ambient and on fp32 environment texels (pbr_context.hip, kFaithfulAmbientHi) keep c + 1 below 2^111
+// without PBR_FLAG_APPLY_AO; with it, only while the AO plane's value is within 2^15 (not checked: DESIGN.md §2).
 __device__ __forceinline__ float reinhard_faithful(float c) { return c * __builtin_amdgcn_rcpf(c + 1.0f); }
 
 // The ambient term of Default.hlsl:139-150 (before the AO extension).

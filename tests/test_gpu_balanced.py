@@ -272,19 +272,27 @@ def test_balanced_range_cut_in_pass1(mode, ctx_pair, gpu):
     check_mode(mode, got, want, ref)
 
 
-@pytest.mark.parametrize("top", [2.0 ** 50, 2.0 ** 51, 1.0e30])
-def test_balanced_exact_strength_bound(top, ctx_pair, gpu):
+@pytest.mark.parametrize("top,low", [(2.0 ** 50, None), (2.0 ** 51, None), (1.0e30, None), (1.0, 1.0e-35),
+                                     (1.0, 2.0 ** -140)],
+                         ids=["1125899906842624.0", "2251799813685248.0", "1e+30", "low1e-35", "low_subnormal"])
+def test_balanced_exact_strength_bound(top, low, ctx_pair, gpu):
     """The exact balanced items run brdf_x2's QUARTER form (N / 4, k / 4, 16 (a^2 - 1), 16 N.V, 4x strengths: exact
-    power-of-two scalings, pbr_balanced.h), whose 4x radiance the host bounds: every point strength within 2^50
-    (pbr_context.hip, points_quarter_ok), else the uniform exact loop. Strengths spanning 2^-20 .. `top` (one light
-    at `top`, one negative, others over 20 decades): bit-identical to the uniform loop and the oracle either way, and
-    the balanced kernel runs exactly when the bound holds."""
+    power-of-two scalings, pbr_balanced.h), whose 4x radiance the host bounds: every point strength 0 or within
+    [2^-34, 2^50] (pbr_context.hip, kQuarterStrengthLo / Hi -> points_quarter_ok), else the uniform exact loop.
+    Strengths spanning 2^-20 .. `top` (one light at `top`, one negative, others over 20 decades) or, with `low`, a
+    pass whose strengths span `low` .. 100 `low` (1e-35, or a subnormal: s att is subnormal in the reference's order
+    and normal in the 4x form): bit-identical to the uniform loop and the oracle either way, and the balanced kernel
+    runs exactly when the bounds hold."""
     rng = np.random.default_rng(71)
     nl = 24
     planes, lights = _scene(rng, 256, 8, nl)
     lights[:, 0:3] = (10.0 ** rng.uniform(-6, 14, (nl, 3))).astype(np.float32)
     lights[3, 0:3] = (top, 1.0, 2.0 ** -20)
     lights[7, 0:3] = (-5.0e3, 0.0, -2.0 ** -30)  # negative and zero strengths scale exactly too
+    if low is not None:  # every strength within two decades of `low`: a larger term would swamp the roundings at stake
+        lights[:, 0:3] = (low * 10.0 ** rng.uniform(0, 2, (nl, 3))).astype(np.float32)
+        lights[3, 0:3] = (low, 1.5 * low, 64.0 * low)
+        lights[7, 0:3] = (-5.0 * low, 0.0, -2.0 * low)
     pc = PassConstants(num_point_lights=nl, lights_array=lights, flags=0)
     gb = GBuffer.from_host(planes, gpu)
     bal, plain = ctx_pair
@@ -292,8 +300,8 @@ def test_balanced_exact_strength_bound(top, ctx_pair, gpu):
     kernel = bal.last_kernel()
     want, redo_p = run(plain, gb, pc)
     ref = O.shade(list(planes), oracle_pass_from_constants(pc), pc.light_array(), None, n_threads=4)
-    print(f"strengths up to {top:g}: {kernel}, redo {redo_b} vs {redo_p}")
-    assert kernel.endswith(", 2>") == (top <= 2.0 ** 50)
+    print(f"strengths up to {top:g}, down to {low}: {kernel}, redo {redo_b} vs {redo_p}")
+    assert kernel.endswith(", 2>") == (top <= 2.0 ** 50 and low is None)
     assert redo_b <= redo_p
     check_mode("exact", got, want, ref)
 

@@ -96,10 +96,12 @@ def test_faithful_golden_vectors(name, shading_ctx, gpu, env_map):
 
 
 @pytest.mark.parametrize("case", ["negative_strength", "negative_ambient", "exact_only", "65_lights",
-                                  "culled_100_lights_in_range"])
+                                  "culled_100_lights_in_range", "tiny_strength", "huge_strength", "huge_ambient"])
 def test_faithful_preconditions_keep_the_pass_exact(case, shading_ctx, gpu):
-    """Where a light term could be negative (strength, ambient) or the sum is longer than the bound
-    allows (> 64 lights) the error bound does not hold: the host turns the mode off and the frame
+    """Where a light term could be negative (strength, ambient), the sum is longer than the bound
+    allows (> 64 lights), a strength is outside [2^-25, 2^50] (a product of the rearranged term underflows,
+    or the reference's radiance overflows) or the constant ambient above 2^100 (the finish's reciprocal
+    underflows) the error bound does not hold: the host turns the mode off and the frame
     equals the default (exact) mode bit for bit."""
     import dataclasses
 
@@ -114,8 +116,14 @@ def test_faithful_preconditions_keep_the_pass_exact(case, shading_ctx, gpu):
         arr = pc.light_array().copy()
         arr[3, 1] = -1.0
         pc = PassConstants(**{**pc.__dict__, "lights_array": arr})
+    elif case in ("tiny_strength", "huge_strength"):
+        arr = pc.light_array().copy()
+        arr[3, 1] = 1.0e-30 if case == "tiny_strength" else 1.0e30
+        pc = PassConstants(**{**pc.__dict__, "lights_array": arr})
     elif case == "negative_ambient":
         pc = PassConstants(**{**pc.__dict__, "ambient_light": (0.03, -0.01, 0.03)})
+    elif case == "huge_ambient":
+        pc = PassConstants(**{**pc.__dict__, "ambient_light": (0.03, 2.0 ** 101, 0.03)})
     extra = N.PBR_FLAG_EXACT_ONLY if case == "exact_only" else 0
     gb = GBuffer.from_host(planes, gpu)
     exact = shade(shading_ctx, gb, with_flags(pc, extra), None)
