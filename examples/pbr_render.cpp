@@ -8,6 +8,9 @@
 //   build/pbr_render --config 3 --steps 50            # timed: one JSON line (--mode faithful: PBR_FLAG_FAITHFUL)
 //   build/pbr_render --config 2 --dump frame.bin      # one frame -> file (tests compare it with the oracle)
 //   build/pbr_render --check-assets                   # decode the assets only (no GPU)
+//   build/pbr_render --config 4 --device-resolve --dump frame.bin   # the host fills the interpolated attributes
+//                                                     # only; Default.hlsl:50-116 (textures, F0, normal map) runs on
+//                                                     # the device (pbr_resolve_materials), then the shading pass
 //
 // Row-partitioned multi-GPU mode (BASELINE config 5; the C++ counterpart of physically_based_renderer_amd/dist.py):
 // one process per GPU, rank / world / local rank from RANK, WORLD_SIZE, LOCAL_RANK (torch.distributed.run
@@ -101,6 +104,7 @@ struct Args {
     std::string output = "rgba32f", mode = "exact", dump, assets = "physically_based_renderer_amd/assets";
     std::string rendezvous;
     bool check_assets = false, rccl = false;
+    bool device_resolve = false;  // --device-resolve (config 4): attributes on the host, materials resolved on the device
 };
 
 Args parse(int argc, char** argv) {
@@ -128,6 +132,7 @@ Args parse(int argc, char** argv) {
         else if (k == "--assets") a.assets = val();
         else if (k == "--check-assets") a.check_assets = true;
         else if (k == "--rccl") a.rccl = true;
+        else if (k == "--device-resolve") a.device_resolve = true;
         else if (k == "--rendezvous") a.rendezvous = val();
         else if (k == "--print-bands") a.print_bands = std::stoi(val());
         else throw std::runtime_error("unknown option " + k);
@@ -136,6 +141,7 @@ Args parse(int argc, char** argv) {
     if (a.output != "rgba32f" && a.output != "rgba8") throw std::runtime_error("--output rgba32f|rgba8");
     if (a.mode != "exact" && a.mode != "faithful") throw std::runtime_error("--mode exact|faithful");
     if (a.bands < 1) throw std::runtime_error("--bands >= 1");
+    if (a.device_resolve && (a.config != 4 || a.rccl)) throw std::runtime_error("--device-resolve: --config 4, no --rccl");
     return a;
 }
 
@@ -472,8 +478,12 @@ int run(const Args& args) {
     PBR_THROW_IF_HIP(hipHostMalloc(reinterpret_cast<void**>(&host), sizeof(float) * pbr::DeviceGBuffer::kPlanes * plane));
     float* planes[pbr::DeviceGBuffer::kPlanes];
     for (int i = 0; i < pbr::DeviceGBuffer::kPlanes; ++i) planes[i] = host + i * plane;
+    std::vector<uint16_t> material_ids(args.device_resolve ? plane : 0);
     const auto t0 = std::chrono::steady_clock::now();
-    PBR_THROW_IF_FAILED(pbr_gbuffer_fill(&scene, 0, H, planes, W, threads));
+    if (args.device_resolve)  // the interpolated VertexOut only (14 planes in `host`): the materials resolve on the device
+        PBR_THROW_IF_FAILED(pbr_attributes_fill(&scene, 0, H, planes, material_ids.data(), W, threads));
+    else
+        PBR_THROW_IF_FAILED(pbr_gbuffer_fill(&scene, 0, H, planes, W, threads));
     const double fill_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 
     // The scene's pass (UpdateMainPassCB's role): lights + constants, then the config's ambient and flags.
@@ -488,7 +498,34 @@ int run(const Args& args) {
     PBR_THROW_IF_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
     pbr::ShadingContext ctx(0);
     pbr::DeviceGBuffer gb(W, H);
-    gb.Upload(host, stream);
+    if (args.device_resolve) {
+        // Config 4's seven *_1K sets as textured materials (diffuse, specular, roughness, normal maps; a metalness
+        // map where the set has one, else g_Metallic = 0), the attributes uploaded, Default.hlsl:50-116 on the device.
+        const pbr_scene_assets& as = assets.c;
+        const size_t T = static_cast<size_t>(as.mat_size) * as.mat_size;
+        std::vector<pbr::Material> materials;
+        std::vector<pbr_texture_desc> textures;
+        for (int m = 0; m < as.num_materials; ++m) {
+            const int32_t base = static_cast<int32_t>(textures.size());
+            textures.push_back({as.mat_albedo + 3 * T * m, as.mat_size, as.mat_size, 3, 0});
+            textures.push_back({as.mat_specular + 3 * T * m, as.mat_size, as.mat_size, 3, 0});
+            textures.push_back({as.mat_metallic + T * m, as.mat_size, as.mat_size, 1, 0});
+            textures.push_back({as.mat_roughness + T * m, as.mat_size, as.mat_size, 1, 0});
+            textures.push_back({as.mat_normal + 3 * T * m, as.mat_size, as.mat_size, 3, 0});
+            pbr::Material mat;
+            mat.Flags = PBR_MAT_DIFFUSE_TEXTURE | PBR_MAT_SPECULAR_TEXTURE | PBR_MAT_ROUGHNESS_TEXTURE | PBR_MAT_NORMAL_TEXTURE;
+            mat.Diffuse_Tex = base, mat.Specular_Tex = base + 1, mat.Roughness_Tex = base + 3, mat.Normal_Tex = base + 4;
+            if (as.mat_has_metallic[m]) mat.Flags |= PBR_MAT_METALLIC_TEXTURE, mat.Metallic_Tex = base + 2;
+            materials.push_back(mat);
+        }
+        ctx.SetMaterials(materials, textures, stream);
+        pbr::DeviceAttributes attrs(W, H);
+        attrs.Upload(host, material_ids.data(), stream);
+        ctx.ResolveMaterials(attrs.View(), gb, 0, PBR_FILTER_POINT, nullptr, nullptr, 0, stream);
+        PBR_THROW_IF_HIP(hipStreamSynchronize(stream));  // `attrs` is released at the end of this block
+    } else {
+        gb.Upload(host, stream);
+    }
     ctx.SetPass(pass, stream);
     if (cfg->ambient == pbr::AmbientMode::IblDiffuse) ctx.SetEnvMap(assets.env.texels.data(), assets.env.width, assets.env.height, stream);
 

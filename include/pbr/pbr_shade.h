@@ -246,6 +246,99 @@ const char* pbr_last_pass_kernel(pbr_context* ctx, void* stream);
  * the first context on the device (or the last reset) counts. PBR_ERR_UNSUPPORTED from a product build. */
 int pbr_debug_bounds(pbr_context* ctx, uint32_t* flags, int reset);
 
+/* ---- Device material resolve: interpolated attributes + material textures -> G-buffer ----------
+ * The first half of PS (Default.hlsl:50-116): normalize(pin.NormalW), the material texture fetches behind the
+ * *_TEXTURE permutation defines, the F0 resolve, NormalSampleToWorldSpace and the ALPHA_TEST opacity fetch, run on
+ * the device so that a caller with real geometry hands over its interpolated VertexOut (Default.hlsl:12-20) and gets
+ * a pbr_gbuffer_soa back without a host round trip.
+ * These entry points are additive: PBR_ABI_VERSION stays 9, and a caller that may meet an older library detects them
+ * by symbol (dlsym), as for pbr_last_pass_kernel. */
+
+enum pbr_material_flags { /* a permutation's defines (Default.hlsl:79-116, PBRApp.cpp:892-963) as bits */
+    PBR_MAT_DIFFUSE_TEXTURE = 1u << 0,   /* DIFFUSE_TEXTURE:   albedo    = tex[0].rgb, else diffuse_albedo */
+    PBR_MAT_SPECULAR_TEXTURE = 1u << 1,  /* SPECULAR_TEXTURE:  F0        = tex[1].rgb, else lerp(fresnel_r0, albedo, metallic) */
+    PBR_MAT_METALLIC_TEXTURE = 1u << 2,  /* METALLIC_TEXTURE:  metallic  = tex[2].r,   else metallic */
+    PBR_MAT_ROUGHNESS_TEXTURE = 1u << 3, /* ROUGHNESS_TEXTURE: roughness = tex[3].r,   else roughness */
+    PBR_MAT_NORMAL_TEXTURE = 1u << 4,    /* NORMAL_TEXTURE:    N = NormalSampleToWorldSpace(tex[4].rgb, ...), else NormalW */
+    PBR_MAT_ALPHA_TEST = 1u << 5         /* ALPHA_TEST:        opacity   = tex[5].r (always point-wrap, Default.hlsl:112),
+                                            else opacity */
+};
+
+#define PBR_MATERIAL_NONE 0xFFFFu /* material id of a background pixel (any id >= the table's count is one too) */
+
+/* One material: the members of cbMaterial PS reads before the light loop (Core.hlsl:64-81, Material.h:10-29) and
+ * the permutation it is drawn with. tex[k] indexes the texture list of pbr_set_materials (the reference's
+ * g_TextureArray slots 0-4 and 11, Default.hlsl:80-112); -1 = unused. */
+typedef struct pbr_material {
+    float diffuse_albedo[3]; /* g_DiffuseAlbedo */
+    float metallic;          /* g_Metallic */
+    float fresnel_r0[3];     /* g_FresnelR0 */
+    float roughness;         /* g_Roughness */
+    float opacity;           /* g_Opacity */
+    uint32_t flags;          /* pbr_material_flags */
+    int32_t tex[6];          /* diffuse, specular, metallic, roughness, normal, opacity */
+} pbr_material;
+
+/* A UNORM8 texture in HOST memory: width*height*channels bytes, row-major, 1, 3 or 4 channels
+ * (a 1-channel texture read as .rgb replicates .r). A texel decodes as (float)u8 / 255.0f. */
+typedef struct pbr_texture_desc {
+    const uint8_t* texels;
+    int32_t width;
+    int32_t height;
+    int32_t channels;
+    int32_t pad0;
+} pbr_texture_desc;
+
+/* Texture filters of the resolve. The reference samples its material maps with g_SamAnisotropicWrap
+ * (Default.hlsl:80-105); anisotropic filtering stays parity-unpinned, so the caller picks one of
+ * the two filters this library pins bit for bit. */
+typedef enum pbr_texture_filter {
+    PBR_FILTER_POINT = 0, /* texel (wrap(floorf(u * W)), wrap(floorf(v * H))) */
+    PBR_FILTER_LINEAR = 1 /* the linear-wrap bilinear of the environment lookup, per channel */
+} pbr_texture_filter;
+
+/* Uploads the material table and its textures (replaces BuildMaterials / LoadTextures, PBRApp.cpp:892-963,
+ * 1196-1463). Same rules as pbr_set_env_map: the host data may be released on return, the previous table is
+ * released only after the queued resolves that read it (on any stream), call it outside a graph capture.
+ * PBR_ERR_INVALID_ARGUMENT: a flag whose tex slot is -1 or >= n_textures, channels not 1, 3 or 4, a non-positive
+ * texture size, n_materials >= 0xFFFF. */
+int pbr_set_materials(pbr_context* ctx, const pbr_material* materials, int32_t n_materials,
+                      const pbr_texture_desc* textures, int32_t n_textures, void* stream);
+
+/* The interpolated VertexOut (Default.hlsl:12-20) per pixel, DEVICE planes, plus the material id of the object
+ * that covers the pixel. One `row_stride` (elements) for all fifteen planes. */
+typedef struct pbr_attributes_soa {
+    const float* pos_w[3];       /* PosW */
+    const float* normal_w[3];    /* NormalW, not normalised (a background pixel: the sky direction) */
+    const float* tangent_w[3];   /* TangentW */
+    const float* bitangent_w[3]; /* BitangentW */
+    const float* tex_coord[2];   /* TexCoord */
+    const uint16_t* material;    /* index into the material table; PBR_MATERIAL_NONE = background */
+    int32_t width;
+    int32_t height;
+    int64_t row_stride;          /* elements; >= width */
+} pbr_attributes_soa;
+
+/* Where the resolve writes: the 15 planes of a pbr_gbuffer_soa (pos xyz, normal xyz, albedo rgb, metallic,
+ * roughness, ao, f0 rgb), the opacity plane and the coverage bytes pbr_shade_frame consumes. DEVICE memory. */
+typedef struct pbr_gbuffer_targets {
+    float* planes[15];
+    float* opacity;              /* may be NULL */
+    uint8_t* coverage;           /* may be NULL; 1 = geometry, 0 = background */
+    int64_t row_stride;          /* elements, planes and opacity; >= width */
+    int64_t coverage_row_stride; /* bytes; >= width when coverage is given */
+} pbr_gbuffer_targets;
+
+/* Default.hlsl:50-116 for every pixel of `attrs` into `targets`, asynchronously on `stream`; `filter` is a
+ * pbr_texture_filter. Position passes through, AO is 1, the F0 plane is always written (shade the result with
+ * PBR_FLAG_F0_PLANE: one pass then carries objects of different permutations). A background pixel gets its
+ * NormalW unchanged in the normal planes, albedo 0, metallic 0, roughness 1, F0 0.04, opacity 1, coverage 0, and
+ * reads no table entry or texel. Rows are independent: a row band resolved through offset pointers equals the same
+ * rows of the full frame. Not a shading pass: pbr_last_pass_stats / _kernel are unchanged by it.
+ * PBR_ERR_NOT_READY before pbr_set_materials. */
+int pbr_resolve_materials(pbr_context* ctx, const pbr_attributes_soa* attrs, const pbr_gbuffer_targets* targets,
+                          int32_t filter, void* stream);
+
 /* ---- Host G-buffer fill (replaces the VS + rasteriser front-end, Default.hlsl:22-45) ---------- */
 
 typedef enum pbr_scene_kind {
@@ -302,6 +395,16 @@ int64_t pbr_gbuffer_fill(const pbr_scene_desc* scene, int32_t row_begin, int32_t
 int64_t pbr_gbuffer_fill_coverage(const pbr_scene_desc* scene, int32_t row_begin, int32_t row_end,
                                   float* const* planes, int64_t row_stride, uint8_t* coverage,
                                   int64_t coverage_stride, int32_t n_threads);
+
+/* The attribute half of pbr_gbuffer_fill for PBR_SCENE_PLANE_MATERIALS and PBR_SCENE_REFERENCE_SPHERES (other
+ * kinds: PBR_ERR_UNSUPPORTED): rows [row_begin, row_end) of the interpolated VertexOut (Default.hlsl:12-20) into 14
+ * HOST planes in pbr_attributes_soa order (pos xyz, normal xyz, tangent xyz, bitangent xyz, uv) and the material id
+ * plane, both with `row_stride` elements per row. Material ids index the table of scenes.scene_materials (config 4:
+ * the cell's *_1K set; the reference scene: the sphere's index, PBR_MATERIAL_NONE for the background, whose normal
+ * planes carry the view direction). pbr_resolve_materials of the result is the device counterpart of the fill.
+ * Returns the number of covered pixels, or a negative pbr_status. */
+int64_t pbr_attributes_fill(const pbr_scene_desc* scene, int32_t row_begin, int32_t row_end, float* const* planes14,
+                            uint16_t* material, int64_t row_stride, int32_t n_threads);
 
 /* The light list and pass constants of a benchmark scene (`n_lights` point lights; kind 1 uses one
  * light at (20, 20, -20), strength 100, PBRApp.cpp:490-491; kind 5 uses the reference's four

@@ -12,6 +12,8 @@
 //   DxException + ThrowIfFailed (d3dUtil.h:130-163)         pbr::ShadeException + PBR_THROW_IF_FAILED
 //   device/PSO creation, UpdateMainPassCB, DrawIndexed      pbr::ShadingContext (RAII over pbr_context)
 //   the G-buffer render targets the lit pass reads          pbr::DeviceGBuffer (15 SoA planes in HBM)
+//   Material + its texture pointers (Material.h:31-69)      pbr::Material, ShadingContext::SetMaterials
+//   the interpolated VertexOut (Default.hlsl:12-20)         pbr::DeviceAttributes, ShadingContext::ResolveMaterials
 //
 // Nothing here computes: every shading call is the gfx950 kernel behind the C ABI. Header-only; link
 // libpbrshade.so and libamdhip64.so.
@@ -19,6 +21,7 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
@@ -77,6 +80,34 @@ struct PassConstants {
 struct MaterialProperties {
     float3 FresnelR0 = {0.04f, 0.04f, 0.04f};
     float Opacity = 1.0f;
+};
+
+// Material (Material.h:31-69) as the first half of PS reads it (Default.hlsl:79-116): the MaterialProperties constants
+// with the reference's defaults, the permutation's defines as Flags (pbr_material_flags) and its textures as indices
+// into the list given to ShadingContext::SetMaterials (-1: none).
+struct Material {
+    float3 Diffuse = {1.0f, 1.0f, 1.0f};
+    float Metallic = 0.0f;
+    float3 FresnelR0 = {0.04f, 0.04f, 0.04f};
+    float Roughness = 1.0f;
+    float Opacity = 1.0f;
+    uint32_t Flags = 0;
+    int32_t Diffuse_Tex = -1, Specular_Tex = -1, Metallic_Tex = -1, Roughness_Tex = -1, Normal_Tex = -1, Opacity_Tex = -1;
+
+    pbr_material ToC() const {
+        pbr_material m;
+        std::memset(&m, 0, sizeof m);
+        const float d[3] = {Diffuse.x, Diffuse.y, Diffuse.z}, f[3] = {FresnelR0.x, FresnelR0.y, FresnelR0.z};
+        std::memcpy(m.diffuse_albedo, d, sizeof d);
+        std::memcpy(m.fresnel_r0, f, sizeof f);
+        m.metallic = Metallic;
+        m.roughness = Roughness;
+        m.opacity = Opacity;
+        m.flags = Flags;
+        const int32_t t[6] = {Diffuse_Tex, Specular_Tex, Metallic_Tex, Roughness_Tex, Normal_Tex, Opacity_Tex};
+        std::memcpy(m.tex, t, sizeof t);
+        return m;
+    }
 };
 
 // DxException (d3dUtil.h:130-143): the failing call, file and line; ToString() like the reference's.
@@ -182,6 +213,76 @@ class DeviceGBuffer {
     int64_t row_stride_ = 0;
 };
 
+// The interpolated VertexOut in HBM (pbr_attributes_soa): 14 fp32 planes (pos xyz, normal xyz, tangent xyz,
+// bitangent xyz, uv) and the 16-bit material id plane, `row_stride` elements per row. Owned here.
+class DeviceAttributes {
+  public:
+    static constexpr int kPlanes = 14;
+
+    DeviceAttributes() = default;
+    DeviceAttributes(int32_t width, int32_t height) : width_(width), height_(height), row_stride_(width) {
+        if (width <= 0 || height < 0)
+            throw ShadeException(PBR_ERR_INVALID_ARGUMENT, "DeviceAttributes", __FILE__, __LINE__, "size");
+        PBR_THROW_IF_HIP(hipMalloc(reinterpret_cast<void**>(&planes_), plane_bytes() * kPlanes));
+        PBR_THROW_IF_HIP(hipMalloc(reinterpret_cast<void**>(&material_), material_bytes()));
+    }
+    DeviceAttributes(const DeviceAttributes&) = delete;
+    DeviceAttributes& operator=(const DeviceAttributes&) = delete;
+    DeviceAttributes(DeviceAttributes&& o) noexcept { *this = std::move(o); }
+    DeviceAttributes& operator=(DeviceAttributes&& o) noexcept {
+        std::swap(planes_, o.planes_);
+        std::swap(material_, o.material_);
+        std::swap(width_, o.width_);
+        std::swap(height_, o.height_);
+        std::swap(row_stride_, o.row_stride_);
+        return *this;
+    }
+    ~DeviceAttributes() {
+        if (planes_) (void)hipFree(planes_);
+        if (material_) (void)hipFree(material_);
+    }
+
+    int32_t width() const { return width_; }
+    int32_t height() const { return height_; }
+    size_t plane_bytes() const { return sizeof(float) * static_cast<size_t>(row_stride_) * std::max(height_, 1); }
+    size_t material_bytes() const { return sizeof(uint16_t) * static_cast<size_t>(row_stride_) * std::max(height_, 1); }
+
+    // Upload host planes laid out like this buffer (plane-major, width elements per row) and the id plane.
+    void Upload(const float* planes, const uint16_t* material, hipStream_t stream = nullptr) {
+        PBR_THROW_IF_HIP(hipMemcpyAsync(planes_, planes, plane_bytes() * kPlanes, hipMemcpyHostToDevice, stream));
+        PBR_THROW_IF_HIP(hipMemcpyAsync(material_, material, material_bytes(), hipMemcpyHostToDevice, stream));
+    }
+
+    // Rows [row_begin, row_end) as a pbr_attributes_soa (pointers offset to the band).
+    pbr_attributes_soa Band(int32_t row_begin, int32_t row_end) const {
+        if (row_begin < 0 || row_end < row_begin || row_end > height_)
+            throw ShadeException(PBR_ERR_INVALID_ARGUMENT, "DeviceAttributes::Band", __FILE__, __LINE__, "rows");
+        pbr_attributes_soa a;
+        std::memset(&a, 0, sizeof a);
+        const size_t off = static_cast<size_t>(row_begin) * row_stride_, ps = static_cast<size_t>(row_stride_) * height_;
+        for (int k = 0; k < 3; ++k) {
+            a.pos_w[k] = planes_ + (0 + k) * ps + off;
+            a.normal_w[k] = planes_ + (3 + k) * ps + off;
+            a.tangent_w[k] = planes_ + (6 + k) * ps + off;
+            a.bitangent_w[k] = planes_ + (9 + k) * ps + off;
+        }
+        a.tex_coord[0] = planes_ + 12 * ps + off;
+        a.tex_coord[1] = planes_ + 13 * ps + off;
+        a.material = material_ + off;
+        a.width = width_;
+        a.height = row_end - row_begin;
+        a.row_stride = row_stride_;
+        return a;
+    }
+    pbr_attributes_soa View() const { return Band(0, height_); }
+
+  private:
+    float* planes_ = nullptr;
+    uint16_t* material_ = nullptr;
+    int32_t width_ = 0, height_ = 0;
+    int64_t row_stride_ = 0;
+};
+
 // One device's shading pipeline: replaces device + PSO creation (d3dApp.cpp:437-501, PBRApp.cpp:607-650,
 // 776-881), UpdateMainPassCB (PBRApp.cpp:455-502), the sky/env SRVs (PBRApp.cpp:1200-1210) and the lit
 // pass's DrawIndexedInstanced (PBRApp.cpp:1133). Calls are asynchronous on the stream given.
@@ -245,6 +346,33 @@ class ShadingContext {
         f.coverage = coverage;
         f.coverage_row_stride = coverage_row_stride;
         Check(pbr_shade_frame(ctx_, &gb, &f, stream), "pbr_shade_frame");
+    }
+
+    // BuildMaterials + LoadTextures (PBRApp.cpp:892-963, 1196-1463): the material table and its UNORM8 textures
+    // (host data reusable on return).
+    void SetMaterials(const std::vector<Material>& materials, const std::vector<pbr_texture_desc>& textures,
+                      hipStream_t stream = nullptr) {
+        std::vector<pbr_material> m;
+        m.reserve(materials.size());
+        for (const Material& x : materials) m.push_back(x.ToC());
+        Check(pbr_set_materials(ctx_, m.data(), static_cast<int32_t>(m.size()), textures.data(),
+                                static_cast<int32_t>(textures.size()), stream),
+              "pbr_set_materials");
+    }
+    // The first half of PS (Default.hlsl:50-116) over the attributes (or a band of them) into the planes of `gb`
+    // (same band), with an optional opacity plane (gb's row stride) and coverage bytes (`coverage_row_stride` each).
+    void ResolveMaterials(const pbr_attributes_soa& attrs, DeviceGBuffer& gb, int32_t row_begin,
+                          pbr_texture_filter filter = PBR_FILTER_POINT, float* opacity = nullptr,
+                          uint8_t* coverage = nullptr, int64_t coverage_row_stride = 0, hipStream_t stream = nullptr) {
+        pbr_gbuffer_targets t;
+        std::memset(&t, 0, sizeof t);
+        const size_t off = static_cast<size_t>(row_begin) * gb.row_stride();
+        for (int i = 0; i < DeviceGBuffer::kPlanes; ++i) t.planes[i] = gb.plane(i) + off;
+        t.opacity = opacity;
+        t.coverage = coverage;
+        t.row_stride = gb.row_stride();
+        t.coverage_row_stride = coverage_row_stride;
+        Check(pbr_resolve_materials(ctx_, &attrs, &t, filter, stream), "pbr_resolve_materials");
     }
 
     pbr_pass_stats LastPassStats(hipStream_t stream = nullptr) {

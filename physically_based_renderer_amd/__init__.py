@@ -5,6 +5,6 @@ LightingUtil.hlsl:35-225) as hand-written HIP kernels behind the C ABI of includ
 """
 from . import _native
 from ._native import PbrError
-from .renderer import GBuffer, Light, PassConstants, ShadingContext
+from .renderer import Attributes, GBuffer, Light, Material, PassConstants, ShadingContext
 
-__all__ = ["GBuffer", "Light", "PassConstants", "PbrError", "ShadingContext", "_native"]
+__all__ = ["Attributes", "GBuffer", "Light", "Material", "PassConstants", "PbrError", "ShadingContext", "_native"]

@@ -39,7 +39,18 @@ PBR_SCENE_RANDOM_COVERED = 2
 PBR_SCENE_PLANE_MATERIALS = 4
 PBR_SCENE_REFERENCE_SPHERES = 5
 
+PBR_MAT_DIFFUSE_TEXTURE = 1 << 0  # pbr_material_flags: a permutation's defines (Default.hlsl:79-116)
+PBR_MAT_SPECULAR_TEXTURE = 1 << 1
+PBR_MAT_METALLIC_TEXTURE = 1 << 2
+PBR_MAT_ROUGHNESS_TEXTURE = 1 << 3
+PBR_MAT_NORMAL_TEXTURE = 1 << 4
+PBR_MAT_ALPHA_TEST = 1 << 5
+PBR_MATERIAL_NONE = 0xFFFF  # material id of a background pixel
+PBR_FILTER_POINT = 0
+PBR_FILTER_LINEAR = 1
+
 NUM_PLANES = 15
+NUM_ATTRIBUTE_PLANES = 14  # pos xyz, normal xyz, tangent xyz, bitangent xyz, uv (pbr_attributes_soa)
 PLANE_NAMES = ("px", "py", "pz", "nx", "ny", "nz", "ar", "ag", "ab",
                "metal", "rough", "ao", "f0r", "f0g", "f0b")
 
@@ -132,6 +143,54 @@ class Camera(ctypes.Structure):
     ]
 
 
+class MaterialDesc(ctypes.Structure):
+    """pbr_material: the cbMaterial members PS reads before the light loop (Core.hlsl:64-81) + its permutation."""
+    _fields_ = [
+        ("diffuse_albedo", ctypes.c_float * 3),
+        ("metallic", ctypes.c_float),
+        ("fresnel_r0", ctypes.c_float * 3),
+        ("roughness", ctypes.c_float),
+        ("opacity", ctypes.c_float),
+        ("flags", ctypes.c_uint32),
+        ("tex", ctypes.c_int32 * 6),
+    ]
+
+
+class TextureDesc(ctypes.Structure):
+    _fields_ = [
+        ("texels", ctypes.c_void_p),
+        ("width", ctypes.c_int32),
+        ("height", ctypes.c_int32),
+        ("channels", ctypes.c_int32),
+        ("pad0", ctypes.c_int32),
+    ]
+
+
+class AttributesSoA(ctypes.Structure):
+    """pbr_attributes_soa: the interpolated VertexOut (Default.hlsl:12-20) + the material id plane."""
+    _fields_ = [
+        ("pos_w", ctypes.c_void_p * 3),
+        ("normal_w", ctypes.c_void_p * 3),
+        ("tangent_w", ctypes.c_void_p * 3),
+        ("bitangent_w", ctypes.c_void_p * 3),
+        ("tex_coord", ctypes.c_void_p * 2),
+        ("material", ctypes.c_void_p),
+        ("width", ctypes.c_int32),
+        ("height", ctypes.c_int32),
+        ("row_stride", ctypes.c_int64),
+    ]
+
+
+class GBufferTargets(ctypes.Structure):
+    _fields_ = [
+        ("planes", ctypes.c_void_p * 15),
+        ("opacity", ctypes.c_void_p),
+        ("coverage", ctypes.c_void_p),
+        ("row_stride", ctypes.c_int64),
+        ("coverage_row_stride", ctypes.c_int64),
+    ]
+
+
 class PassStats(ctypes.Structure):
     """pbr_pass_stats: statistics of the last shading pass."""
     _fields_ = [
@@ -179,6 +238,13 @@ SIGNATURES = {
     "pbr_last_pass_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(PassStats), ctypes.c_void_p]),
     "pbr_last_pass_kernel": (ctypes.c_char_p, [ctypes.c_void_p, ctypes.c_void_p]),
     "pbr_debug_bounds": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
+    "pbr_set_materials": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(MaterialDesc), ctypes.c_int32,
+                                         ctypes.POINTER(TextureDesc), ctypes.c_int32, ctypes.c_void_p]),
+    "pbr_resolve_materials": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(AttributesSoA),
+                                             ctypes.POINTER(GBufferTargets), ctypes.c_int32, ctypes.c_void_p]),
+    "pbr_attributes_fill": (ctypes.c_int64, [ctypes.POINTER(SceneDesc), ctypes.c_int32, ctypes.c_int32,
+                                             ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.c_int64,
+                                             ctypes.c_int32]),
     "pbr_gbuffer_fill": (ctypes.c_int64, [ctypes.POINTER(SceneDesc), ctypes.c_int32, ctypes.c_int32,
                                           ctypes.POINTER(ctypes.c_void_p), ctypes.c_int64, ctypes.c_int32]),
     "pbr_gbuffer_fill_coverage": (ctypes.c_int64, [ctypes.POINTER(SceneDesc), ctypes.c_int32, ctypes.c_int32,

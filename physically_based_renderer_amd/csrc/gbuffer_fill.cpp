@@ -233,32 +233,51 @@ Basis camera_basis(const pbr_scene_desc& sc) {
     return b;
 }
 
+// The ray cast of one pixel of the reference scene, shared by the G-buffer fill and the attribute fill
+// (pbr_attributes_fill): the unit view direction and the nearest sphere hit.
+struct RefCast {
+    double d[3];
+    double best;
+    int hit;  // sphere index, -1 = background
+};
+
+inline RefCast cast_reference(const pbr_scene_desc& sc, const Basis& b, double aspect, int x, int y) {
+    RefCast rc;
+    const double sx = (2.0 * (x + 0.5) / sc.width - 1.0) * b.t * aspect, sy = (1.0 - 2.0 * (y + 0.5) / sc.height) * b.t;
+    double* d = rc.d;
+    for (int i = 0; i < 3; ++i) d[i] = b.f[i] + sx * b.r[i] + sy * b.u[i];
+    const double dl = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+    for (int i = 0; i < 3; ++i) d[i] /= dl;
+    // nearest hit within the camera's [near, far] = [0.1, 100] (BuildCamera, PBRApp.cpp:654)
+    double best = 100.0;
+    int hit = -1;
+    for (int s = 0; s < kRefSpheres; ++s) {
+        const RefSphere sp = ref_sphere(s);
+        const double o[3] = {b.eye[0] - sp.cx, b.eye[1] - sp.cy, b.eye[2]};
+        const double bb = o[0] * d[0] + o[1] * d[1] + o[2] * d[2];
+        const double cc = o[0] * o[0] + o[1] * o[1] + o[2] * o[2] - 1.0;
+        const double disc = bb * bb - cc;
+        if (disc < 0.0) continue;
+        const double sq = std::sqrt(disc);
+        double tt = -bb - sq;
+        if (tt < 0.1) tt = -bb + sq;  // eye inside / behind the near plane: the far side
+        if (tt >= 0.1 && tt < best) best = tt, hit = s;
+    }
+    rc.best = best;
+    rc.hit = hit;
+    return rc;
+}
+
 void fill_reference(const pbr_scene_desc& sc, int y, Row r) {
     const pbr_scene_assets* as = sc.assets;
     const Basis b = camera_basis(sc);
     const double aspect = (double)sc.width / (double)sc.height;
     const int T = as->mat_size, RS = as->rust_size;
     for (int x = 0; x < sc.width; ++x) {
-        const double sx = (2.0 * (x + 0.5) / sc.width - 1.0) * b.t * aspect, sy = (1.0 - 2.0 * (y + 0.5) / sc.height) * b.t;
-        double d[3];
-        for (int i = 0; i < 3; ++i) d[i] = b.f[i] + sx * b.r[i] + sy * b.u[i];
-        const double dl = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-        for (int i = 0; i < 3; ++i) d[i] /= dl;
-        // nearest hit within the camera's [near, far] = [0.1, 100] (BuildCamera, PBRApp.cpp:654)
-        double best = 100.0;
-        int hit = -1;
-        for (int s = 0; s < kRefSpheres; ++s) {
-            const RefSphere sp = ref_sphere(s);
-            const double o[3] = {b.eye[0] - sp.cx, b.eye[1] - sp.cy, b.eye[2]};
-            const double bb = o[0] * d[0] + o[1] * d[1] + o[2] * d[2];
-            const double cc = o[0] * o[0] + o[1] * o[1] + o[2] * o[2] - 1.0;
-            const double disc = bb * bb - cc;
-            if (disc < 0.0) continue;
-            const double sq = std::sqrt(disc);
-            double tt = -bb - sq;
-            if (tt < 0.1) tt = -bb + sq;  // eye inside / behind the near plane: the far side
-            if (tt >= 0.1 && tt < best) best = tt, hit = s;
-        }
+        const RefCast rc = cast_reference(sc, b, aspect, x, y);
+        const double* d = rc.d;
+        const double best = rc.best;
+        const int hit = rc.hit;
         set_cov(r, x, hit >= 0);
         r.p[kAo][x] = 1.0f;
         if (hit < 0) {  // background: the view direction for the sky pass (Skybox.hlsl:24, 41)
@@ -332,6 +351,73 @@ void fill_reference(const pbr_scene_desc& sc, int y, Row r) {
     }
 }
 
+// ---- Attribute fills (pbr_attributes_fill): the interpolated VertexOut the fills above consume in place ----------
+struct AttrRow {
+    float* p[14];  // pos xyz, normal xyz, tangent xyz, bitangent xyz, uv
+    uint16_t* mat;
+};
+
+// Config 4 (fill_plane): UV at the texel centre of the cell-tiled maps, the plane's frame T = +x, B = -z, N = +y.
+void attrs_plane(const pbr_scene_desc& sc, int y, AttrRow r) {
+    const pbr_scene_assets* as = sc.assets;
+    const int T = as->mat_size, M = as->num_materials;
+    const float s = 1000.0f / (float)sc.height;
+    for (int x = 0; x < sc.width; ++x) {
+        r.p[0][x] = ((float)x + 0.5f - 0.5f * (float)sc.width) * s;
+        r.p[1][x] = 0.0f;
+        r.p[2][x] = (0.5f * (float)sc.height - ((float)y + 0.5f)) * s;
+        const uint64_t cell = (uint64_t)(y / 64) * 65536u + (uint64_t)(x / 64);
+        r.mat[x] = (uint16_t)(splitmix64(sc.seed ^ (cell * 0x9E3779B97F4A7C15ull)) % (uint64_t)M);
+        r.p[3][x] = 0.0f, r.p[4][x] = 1.0f, r.p[5][x] = 0.0f;
+        r.p[6][x] = 1.0f, r.p[7][x] = 0.0f, r.p[8][x] = 0.0f;
+        r.p[9][x] = 0.0f, r.p[10][x] = 0.0f, r.p[11][x] = -1.0f;
+        r.p[12][x] = ((float)(x % T) + 0.5f) / (float)T;
+        r.p[13][x] = ((float)(y % T) + 0.5f) / (float)T;
+    }
+}
+
+// The reference scene (fill_reference): NormalW = P - C unnormalised (PS normalises it, Default.hlsl:50), SphereMesh's
+// T and B, UV; the material id is the sphere's index.
+int64_t attrs_reference(const pbr_scene_desc& sc, int y, AttrRow r) {
+    const Basis b = camera_basis(sc);
+    const double aspect = (double)sc.width / (double)sc.height;
+    int64_t covered = 0;
+    for (int x = 0; x < sc.width; ++x) {
+        const RefCast rc = cast_reference(sc, b, aspect, x, y);
+        const double* d = rc.d;
+        if (rc.hit < 0) {  // background: the view direction in the normal planes, as the G-buffer fill
+            r.p[0][x] = (float)(b.eye[0] + d[0] * 100.0);
+            r.p[1][x] = (float)(b.eye[1] + d[1] * 100.0);
+            r.p[2][x] = (float)(b.eye[2] + d[2] * 100.0);
+            r.p[3][x] = (float)d[0], r.p[4][x] = (float)d[1], r.p[5][x] = (float)d[2];
+            for (int i = 6; i < 14; ++i) r.p[i][x] = 0.0f;
+            r.mat[x] = PBR_MATERIAL_NONE;
+            continue;
+        }
+        ++covered;
+        const RefSphere sp = ref_sphere(rc.hit);
+        const double P[3] = {b.eye[0] + d[0] * rc.best, b.eye[1] + d[1] * rc.best, b.eye[2] + d[2] * rc.best};
+        const double q[3] = {P[0] - sp.cx, P[1] - sp.cy, P[2]};
+        const double ql = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2]);
+        const float nw[3] = {(float)(q[0] / ql), (float)(q[1] / ql), (float)(q[2] / ql)};
+        double theta = std::atan2(q[2], q[0]);
+        if (theta < 0.0) theta += 2.0 * M_PI;
+        const double uu = theta / (2.0 * M_PI), vv = std::acos(std::fmin(std::fmax(q[1] / ql, -1.0), 1.0)) / M_PI;
+        const float tg[3] = {(float)-q[2], 0.0f, (float)q[0]};  // dP/dtheta
+        const float bt[3] = {nw[1] * tg[2] - nw[2] * tg[1], nw[2] * tg[0] - nw[0] * tg[2], nw[0] * tg[1] - nw[1] * tg[0]};
+        for (int c = 0; c < 3; ++c) {
+            r.p[c][x] = (float)P[c];
+            r.p[3 + c][x] = (float)q[c];
+            r.p[6 + c][x] = tg[c];
+            r.p[9 + c][x] = bt[c];
+        }
+        r.p[12][x] = (float)uu;
+        r.p[13][x] = (float)vv;
+        r.mat[x] = (uint16_t)rc.hit;
+    }
+    return covered;
+}
+
 bool assets_ok(const pbr_scene_desc* sc) {
     const pbr_scene_assets* as = sc->assets;
     if (!as) return false;
@@ -391,6 +477,46 @@ extern "C" int64_t pbr_gbuffer_fill_coverage(const pbr_scene_desc* scene, int32_
             }
             if (r.cov && scene->kind != PBR_SCENE_SPHERE_RUSTEDIRON && scene->kind != PBR_SCENE_REFERENCE_SPHERES)
                 std::memset(r.cov, 1, (size_t)scene->width);
+        }
+    };
+    std::vector<std::thread> th;
+    for (int t = 1; t < nt; ++t) th.emplace_back(work, t);
+    work(0);
+    for (auto& x : th) x.join();
+    int64_t total = 0;
+    for (auto c : covered) total += c;
+    return total;
+}
+
+extern "C" int64_t pbr_attributes_fill(const pbr_scene_desc* scene, int32_t row_begin, int32_t row_end,
+                                       float* const* planes14, uint16_t* material, int64_t row_stride,
+                                       int32_t n_threads) {
+    if (!scene || !planes14 || !material || scene->width <= 0 || scene->height <= 0) return PBR_ERR_INVALID_ARGUMENT;
+    if (row_begin < 0 || row_end < row_begin || row_end > scene->height || row_stride < scene->width)
+        return PBR_ERR_INVALID_ARGUMENT;
+    if (scene->kind != PBR_SCENE_PLANE_MATERIALS && scene->kind != PBR_SCENE_REFERENCE_SPHERES)
+        return PBR_ERR_UNSUPPORTED;
+    if (!assets_ok(scene)) return PBR_ERR_INVALID_ARGUMENT;
+    for (int i = 0; i < 14; ++i)
+        if (!planes14[i]) return PBR_ERR_INVALID_ARGUMENT;
+    const int rows = row_end - row_begin;
+    if (rows == 0) return 0;
+    int nt = n_threads < 1 ? 1 : n_threads;
+    if (nt > rows) nt = rows;
+    if (nt > 256) nt = 256;
+    std::vector<int64_t> covered(nt, 0);
+    auto work = [&](int t) {
+        const int r0 = row_begin + (int)((int64_t)rows * t / nt), r1 = row_begin + (int)((int64_t)rows * (t + 1) / nt);
+        for (int y = r0; y < r1; ++y) {
+            AttrRow r;
+            for (int i = 0; i < 14; ++i) r.p[i] = planes14[i] + (int64_t)(y - row_begin) * row_stride;
+            r.mat = material + (int64_t)(y - row_begin) * row_stride;
+            if (scene->kind == PBR_SCENE_REFERENCE_SPHERES) {
+                covered[t] += attrs_reference(*scene, y, r);
+            } else {
+                attrs_plane(*scene, y, r);
+                covered[t] += scene->width;
+            }
         }
     };
     std::vector<std::thread> th;

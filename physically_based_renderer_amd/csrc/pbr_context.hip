@@ -148,6 +148,17 @@ struct pbr_context {
         Resource use;
     };
     Texture env, sky;
+    // The material table and its textures (pbr_set_materials; read by pbr_resolve_materials): the records and one
+    // RGBA8 texel buffer holding every texture, replaced as a whole.
+    struct Materials {
+        pbr::MaterialRec* d_table = nullptr;
+        uint32_t* d_texels = nullptr;
+        int n = 0;
+        int64_t n_texels = 0;
+        bool set = false;
+        Resource use;
+    };
+    Materials mats;
     // Current pass.
     pbr::PassArgs pass{};
     int ambient_mode = 0;
@@ -327,6 +338,8 @@ void forget_readers(pbr_context* ctx) {
         t->use.readers.clear();
         t->use.writer = -1;
     }
+    ctx->mats.use.readers.clear();
+    ctx->mats.use.writer = -1;
 }
 
 }  // namespace
@@ -416,6 +429,9 @@ int pbr_context_destroy(pbr_context* ctx) {
             if (t->d) (void)hipFreeAsync(t->d, nullptr);
             if (t->use.written) (void)hipEventDestroy(t->use.written);
         }
+        if (ctx->mats.d_table) (void)hipFreeAsync(ctx->mats.d_table, nullptr);
+        if (ctx->mats.d_texels) (void)hipFreeAsync(ctx->mats.d_texels, nullptr);
+        if (ctx->mats.use.written) (void)hipEventDestroy(ctx->mats.use.written);
         for (StreamState& st : ctx->streams) {
             if (st.last_pass) (void)hipEventDestroy(st.last_pass);
             if (st.d_stats) (void)hipFree(st.d_stats);
@@ -769,6 +785,159 @@ int pbr_shade_gbuffer(pbr_context* ctx, const pbr_gbuffer_soa* gb, float* out_rg
 
 int pbr_shade_frame(pbr_context* ctx, const pbr_gbuffer_soa* gb, const pbr_frame_desc* frame, void* stream) {
     return shade(ctx, gb, frame, stream);
+}
+
+}  // extern "C"
+
+// ---- Material resolve (Default.hlsl:50-116 on the device; material_resolve.h) ----------------------------------------
+
+extern "C" {
+
+int pbr_set_materials(pbr_context* ctx, const pbr_material* materials, int32_t n_materials,
+                      const pbr_texture_desc* textures, int32_t n_textures, void* stream) {
+    if (!ctx || n_materials < 0 || n_materials >= (int32_t)PBR_MATERIAL_NONE || n_textures < 0)
+        return PBR_ERR_INVALID_ARGUMENT;
+    if ((n_materials > 0 && !materials) || (n_textures > 0 && !textures)) return PBR_ERR_INVALID_ARGUMENT;
+    // Texture placement in the one RGBA8 buffer; per texture at most 2^26 texels (as the env maps), 2^28 in all.
+    std::vector<pbr::MaterialTex> place((size_t)n_textures);
+    int64_t total = 0;
+    for (int32_t i = 0; i < n_textures; ++i) {
+        const pbr_texture_desc& t = textures[i];
+        if (!t.texels || t.width <= 0 || t.height <= 0) return PBR_ERR_INVALID_ARGUMENT;
+        if (t.channels != 1 && t.channels != 3 && t.channels != 4) return PBR_ERR_INVALID_ARGUMENT;
+        const int64_t n = (int64_t)t.width * t.height;
+        if (n > (1ll << 26) || total + n > (1ll << 28)) return PBR_ERR_INVALID_ARGUMENT;
+        place[(size_t)i] = pbr::MaterialTex{(uint32_t)total, t.width, t.height};
+        total += n;
+    }
+    constexpr uint32_t known = PBR_MAT_DIFFUSE_TEXTURE | PBR_MAT_SPECULAR_TEXTURE | PBR_MAT_METALLIC_TEXTURE |
+                               PBR_MAT_ROUGHNESS_TEXTURE | PBR_MAT_NORMAL_TEXTURE | PBR_MAT_ALPHA_TEST;
+    // tex[] slot of each flag bit: g_TextureArray 0 diffuse, 1 specular, 2 metallic, 3 roughness, 4 normal, 11 opacity
+    static const int slot_of_bit[6] = {0, 1, 2, 3, 4, 5};
+    std::vector<pbr::MaterialRec> recs((size_t)(n_materials > 0 ? n_materials : 1));
+    std::memset(recs.data(), 0, sizeof(pbr::MaterialRec) * recs.size());
+    for (int32_t i = 0; i < n_materials; ++i) {
+        const pbr_material& m = materials[i];
+        if (m.flags & ~known) return PBR_ERR_INVALID_ARGUMENT;
+        pbr::MaterialRec& r = recs[(size_t)i];
+        for (int c = 0; c < 3; ++c) r.diffuse[c] = m.diffuse_albedo[c], r.fresnel[c] = m.fresnel_r0[c];
+        r.metallic = m.metallic;
+        r.roughness = m.roughness;
+        r.opacity = m.opacity;
+        r.flags = m.flags;
+        for (int k = 0; k < 6; ++k) r.tex[k] = pbr::MaterialTex{0u, 1, 1};
+        for (int b = 0; b < 6; ++b) {
+            if (!(m.flags & (1u << b))) continue;
+            const int32_t t = m.tex[slot_of_bit[b]];
+            if (t < 0 || t >= n_textures) return PBR_ERR_INVALID_ARGUMENT;
+            r.tex[slot_of_bit[b]] = place[(size_t)t];
+        }
+    }
+    // Repack to RGBA8: one aligned dword per tap whatever the channel count; a gray texture replicates .r.
+    std::vector<uint32_t> texels((size_t)(total > 0 ? total : 1), 0u);
+    for (int32_t i = 0; i < n_textures; ++i) {
+        const pbr_texture_desc& t = textures[i];
+        uint32_t* dst = texels.data() + place[(size_t)i].offset;
+        const size_t n = (size_t)t.width * (size_t)t.height;
+        for (size_t k = 0; k < n; ++k) {
+            const uint8_t* p = t.texels + k * (size_t)t.channels;
+            const uint32_t r = p[0], g = t.channels == 1 ? p[0] : p[1], b = t.channels == 1 ? p[0] : p[2],
+                           a = t.channels == 4 ? p[3] : 255u;
+            dst[k] = r | (g << 8) | (b << 16) | (a << 24);
+        }
+    }
+
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DeviceGuard g(ctx->device);
+    if (!g.ok) return PBR_ERR_NO_DEVICE;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipError_t e = hipSuccess;
+    const int si = stream_index(ctx, s, e);
+    if (si < 0) return fail_hip(ctx, e, "pbr_set_materials stream");
+    pbr_context::Materials& mt = ctx->mats;
+    // The old table and texels may still be read by queued resolves: released after them, in stream order.
+    e = free_after_readers(ctx, mt.use, mt.d_table, s, si);
+    if (e == hipSuccess && mt.d_texels) e = hipFreeAsync(mt.d_texels, s);
+    if (e != hipSuccess) return fail_hip(ctx, e, "pbr_set_materials release");
+    mt.d_table = nullptr;
+    mt.d_texels = nullptr;
+    mt.set = false;
+    e = hipMallocAsync(reinterpret_cast<void**>(&mt.d_table), sizeof(pbr::MaterialRec) * recs.size(), s);
+    if (e == hipSuccess) e = hipMallocAsync(reinterpret_cast<void**>(&mt.d_texels), sizeof(uint32_t) * texels.size(), s);
+    if (e != hipSuccess) return fail_hip(ctx, e, "pbr_set_materials hipMalloc");
+    e = hipMemcpyAsync(mt.d_table, recs.data(), sizeof(pbr::MaterialRec) * recs.size(), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(mt.d_texels, texels.data(), sizeof(uint32_t) * texels.size(), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);  // the staging copies above are released on return
+    if (e != hipSuccess) return fail_hip(ctx, e, "pbr_set_materials copy");
+    mt.use.writer = -1;  // complete: later resolves on any stream see the new table
+    mt.n = n_materials;
+    mt.n_texels = (int64_t)texels.size();
+    mt.set = true;
+    return PBR_OK;
+}
+
+int pbr_resolve_materials(pbr_context* ctx, const pbr_attributes_soa* at, const pbr_gbuffer_targets* tg, int32_t filter,
+                          void* stream) {
+    if (!ctx || !at || !tg) return PBR_ERR_INVALID_ARGUMENT;
+    if (at->width < 0 || at->height < 0 || at->row_stride < at->width || tg->row_stride < at->width)
+        return PBR_ERR_INVALID_ARGUMENT;
+    if (filter != PBR_FILTER_POINT && filter != PBR_FILTER_LINEAR) return PBR_ERR_INVALID_ARGUMENT;
+    if (tg->coverage && tg->coverage_row_stride < at->width) return PBR_ERR_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (!ctx->mats.set) return PBR_ERR_NOT_READY;
+    if (at->width == 0 || at->height == 0) return PBR_OK;  // empty frame: nothing is read or written
+    pbr::ResolveArgs a{};
+    const float* in[14] = {at->pos_w[0],     at->pos_w[1],     at->pos_w[2],       at->normal_w[0],    at->normal_w[1],
+                           at->normal_w[2],  at->tangent_w[0], at->tangent_w[1],   at->tangent_w[2],   at->bitangent_w[0],
+                           at->bitangent_w[1], at->bitangent_w[2], at->tex_coord[0], at->tex_coord[1]};
+    a.vec = (at->row_stride % 2) == 0 && (tg->row_stride % 2) == 0;
+    for (int i = 0; i < 14; ++i) {
+        if (!in[i] || !aligned(in[i], 4)) return PBR_ERR_INVALID_ARGUMENT;
+        a.attr[i] = in[i];
+        a.vec = a.vec && aligned(in[i], 8);
+    }
+    if (!at->material || !aligned(at->material, 2)) return PBR_ERR_INVALID_ARGUMENT;
+    a.material = at->material;
+    a.vec = a.vec && aligned(at->material, 4);
+    for (int i = 0; i < 15; ++i) {
+        if (!tg->planes[i] || !aligned(tg->planes[i], 4)) return PBR_ERR_INVALID_ARGUMENT;
+        a.plane[i] = tg->planes[i];
+        a.vec = a.vec && aligned(tg->planes[i], 8);
+    }
+    if (tg->opacity && !aligned(tg->opacity, 4)) return PBR_ERR_INVALID_ARGUMENT;
+    a.opacity = tg->opacity;
+    a.coverage = tg->coverage;
+    a.vec = a.vec && aligned(tg->opacity, 8) && aligned(tg->coverage, 2) &&
+            (!tg->coverage || (tg->coverage_row_stride % 2) == 0);
+    a.width = at->width;
+    a.height = at->height;
+    a.in_stride = at->row_stride;
+    a.out_stride = tg->row_stride;
+    a.cov_stride = tg->coverage ? tg->coverage_row_stride : 0;
+    a.table = ctx->mats.d_table;
+    a.n_materials = ctx->mats.n;
+    a.texels = ctx->mats.d_texels;
+    a.n_texels = ctx->mats.n_texels;
+    a.linear = filter == PBR_FILTER_LINEAR;
+
+    DeviceGuard g(ctx->device);
+    if (!g.ok) return PBR_ERR_NO_DEVICE;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipError_t e = hipSuccess;
+    const int si = stream_index(ctx, s, e);
+    if (si < 0) return fail_hip(ctx, e, "pbr_resolve_materials stream");
+    e = before_read(ctx->mats.use, s, si);
+    if (e != hipSuccess) return fail_hip(ctx, e, "pbr_resolve_materials order");
+    e = pbr::launch_resolve_materials(a, s);
+    if (e != hipSuccess) return fail_hip(ctx, e, "resolve_materials_kernel launch", PBR_ERR_LAUNCH);
+    // Not a shading pass: the stream's statistics record, its kernel name and the context's last pass stay as they
+    // are; only the event that orders a later pbr_set_materials after this read is recorded.
+    if (ctx->streams.size() > 1) {
+        e = hipEventRecord(ctx->streams[si].last_pass, s);
+        if (e != hipSuccess) return fail_hip(ctx, e, "pbr_resolve_materials record");
+    }
+    return PBR_OK;
 }
 
 }  // extern "C"

@@ -99,4 +99,43 @@ hipError_t debug_wave_timeline(unsigned long long* buf, long long cap);  // PBR_
 hipError_t debug_bounds_publish(uint32_t* buf);  // PBR_DEBUG_BOUNDS builds only (pbr_debug_bounds.h)
 hipError_t launch_decode_unorm16(const uint16_t* src, float4* dst, int n_texels, hipStream_t stream);
 
+// ---- Material resolve (material_resolve.h; pbr_resolve_materials) ----------------------------------------------
+// pbr_material_flags.
+constexpr uint32_t kMatDiffuseTexture = 1u << 0, kMatSpecularTexture = 1u << 1, kMatMetallicTexture = 1u << 2,
+                   kMatRoughnessTexture = 1u << 3, kMatNormalTexture = 1u << 4, kMatAlphaTest = 1u << 5;
+
+// One texture of a material record: its first texel in the context's RGBA8 texel buffer and its size.
+struct MaterialTex {
+    uint32_t offset;
+    int32_t w, h;
+};
+// The device copy of a pbr_material: constants, permutation flags and the six texture slots (diffuse, specular,
+// metallic, roughness, normal, opacity); an unused slot is {0, 1, 1} and is never sampled.
+struct MaterialRec {
+    float diffuse[3];
+    float metallic;
+    float fresnel[3];
+    float roughness;
+    float opacity;
+    uint32_t flags;
+    MaterialTex tex[6];
+};
+
+struct ResolveArgs {
+    const float* attr[14];     // pbr_attributes_soa order: pos xyz, normal xyz, tangent xyz, bitangent xyz, uv
+    const uint16_t* material;  // ids; >= n_materials = background
+    float* plane[15];          // pbr_gbuffer_soa order
+    float* opacity;            // or nullptr
+    uint8_t* coverage;         // or nullptr
+    int width, height;
+    int64_t in_stride, out_stride, cov_stride;
+    const MaterialRec* table;
+    int n_materials;
+    const uint32_t* texels;    // every texture, RGBA8
+    int64_t n_texels;
+    bool linear;               // PBR_FILTER_LINEAR (else point)
+    bool vec;  // every plane 8-byte aligned, ids 4-byte, coverage 2-byte, every stride even: paired accesses
+};
+hipError_t launch_resolve_materials(const ResolveArgs& a, hipStream_t stream);
+
 }  // namespace pbr

@@ -156,6 +156,79 @@ class GBuffer:
         return g
 
 
+@dataclass
+class Material:
+    """``Material`` / ``MaterialProperties`` (Material.h:10-69) as PS reads them before the light loop
+    (Core.hlsl:64-81, Default.hlsl:79-116): the constants with the reference's defaults, the permutation as
+    ``flags`` (``N.PBR_MAT_*``) and ``tex``, indices into the texture list of :meth:`ShadingContext.set_materials`
+    in the order diffuse, specular, metallic, roughness, normal, opacity (-1: unused)."""
+    diffuse_albedo: Sequence[float] = (1.0, 1.0, 1.0)
+    metallic: float = 0.0
+    fresnel_r0: Sequence[float] = (0.04, 0.04, 0.04)
+    roughness: float = 1.0
+    opacity: float = 1.0
+    flags: int = 0
+    tex: Sequence[int] = (-1, -1, -1, -1, -1, -1)
+
+    def to_c(self) -> N.MaterialDesc:
+        m = N.MaterialDesc()
+        m.diffuse_albedo[:] = [float(v) for v in self.diffuse_albedo]
+        m.metallic = float(self.metallic)
+        m.fresnel_r0[:] = [float(v) for v in self.fresnel_r0]
+        m.roughness = float(self.roughness)
+        m.opacity = float(self.opacity)
+        m.flags = int(self.flags)
+        m.tex[:] = [int(v) for v in self.tex]
+        return m
+
+
+class Attributes:
+    """The interpolated ``VertexOut`` (Default.hlsl:12-20) per pixel on the device: one (14, H, row_stride) fp32
+    tensor, plane order pos xyz, normal xyz, tangent xyz, bitangent xyz, uv (pbr_attributes_soa), and an
+    (H, row_stride) 16-bit material id plane with the same row stride (``N.PBR_MATERIAL_NONE`` = background)."""
+
+    def __init__(self, planes: torch.Tensor, material: torch.Tensor, width: Optional[int] = None):
+        if planes.dim() != 3 or planes.shape[0] != N.NUM_ATTRIBUTE_PLANES or planes.dtype != torch.float32:
+            raise ValueError("planes must be a (14, H, W) float32 tensor")
+        if planes.stride(2) != 1:
+            raise ValueError("planes rows must be contiguous")
+        if (material.dim() != 2 or material.element_size() != 2 or material.is_floating_point() or
+                material.shape[0] != planes.shape[1] or material.shape[1] < planes.shape[2] or
+                material.stride(1) != 1 or material.stride(0) != planes.stride(1) or
+                material.device != planes.device):
+            raise ValueError("material must be an (H, W) 16-bit integer plane with the planes' row stride and device")
+        self.planes = planes
+        self.material = material
+        self.height = planes.shape[1]
+        self.width = planes.shape[2] if width is None else width
+        self.row_stride = planes.stride(1)
+
+    @classmethod
+    def from_host(cls, planes: np.ndarray, material: np.ndarray, device) -> "Attributes":
+        t = torch.from_numpy(np.ascontiguousarray(planes, dtype=np.float32))
+        # torch has no portable uint16: the ids travel as the same bits in int16
+        m = torch.from_numpy(np.ascontiguousarray(material, dtype=np.uint16).view(np.int16))
+        return cls(t.to(device), m.to(device))
+
+    def rows(self, r0: int, r1: int) -> "Attributes":
+        """A row band (a view)."""
+        return Attributes(self.planes[:, r0:r1, :], self.material[r0:r1], self.width)
+
+    def to_c(self) -> N.AttributesSoA:
+        a = N.AttributesSoA()
+        base = self.planes.data_ptr()
+        ps = self.planes.stride(0) * 4
+        ptr = [base + i * ps for i in range(N.NUM_ATTRIBUTE_PLANES)]
+        a.pos_w[:] = ptr[0:3]
+        a.normal_w[:] = ptr[3:6]
+        a.tangent_w[:] = ptr[6:9]
+        a.bitangent_w[:] = ptr[9:12]
+        a.tex_coord[:] = ptr[12:14]
+        a.material = self.material.data_ptr()
+        a.width, a.height, a.row_stride = int(self.width), int(self.height), int(self.row_stride)
+        return a
+
+
 def _stream_handle(stream) -> int:
     if stream is None:
         stream = torch.cuda.current_stream()
@@ -220,6 +293,60 @@ class ShadingContext:
     def set_sky_map(self, texels: np.ndarray, stream=None) -> None:
         """Sky texture (g_SkyArray[0]) sampled for background pixels: uint16 UNORM or float32 RGBA."""
         self._set_texture("pbr_set_sky_map", texels, stream)
+
+    def set_materials(self, materials: Sequence[Material], textures: Sequence[np.ndarray] = (), stream=None) -> None:
+        """Upload the material table and its textures (pbr_set_materials; BuildMaterials / LoadTextures,
+        PBRApp.cpp:892-963, 1196-1463). ``textures``: uint8 arrays, (h, w) or (h, w, c) with c in {1, 3, 4}."""
+        tex = []
+        for t in textures:
+            t = np.asarray(t)
+            if t.dtype != np.uint8 or t.ndim not in (2, 3):
+                raise ValueError("textures must be uint8 arrays of shape (h, w) or (h, w, channels)")
+            tex.append(np.ascontiguousarray(t if t.ndim == 3 else t[:, :, None]))
+        mats = (N.MaterialDesc * max(len(materials), 1))(*[m.to_c() for m in materials])
+        descs = (N.TextureDesc * max(len(tex), 1))()
+        for d, t in zip(descs, tex):
+            d.texels, d.height, d.width, d.channels = t.ctypes.data, t.shape[0], t.shape[1], t.shape[2]
+        N.check(self.lib.pbr_set_materials(self._h, mats, len(materials), descs, len(tex),
+                                           ctypes.c_void_p(_stream_handle(stream))), "pbr_set_materials", self._h)
+
+    def resolve(self, attrs: Attributes, filter: int = N.PBR_FILTER_POINT, out=None, stream=None):
+        """The first half of PS (Default.hlsl:50-116) on the device (pbr_resolve_materials): ``attrs`` and the
+        materials of :meth:`set_materials` into a G-buffer, asynchronously. Returns ``(GBuffer, coverage)``: the
+        G-buffer carries the resolved opacity plane and feeds :meth:`shade` / :meth:`shade_frame` as it is (set the
+        pass with ``PBR_FLAG_F0_PLANE``); ``coverage`` is the (H, W) uint8 plane of ``shade_frame``. ``out``: a
+        ``GBuffer`` or a ``(GBuffer, coverage)`` pair to write into (an absent opacity or coverage plane is not
+        written); default: fresh tensors."""
+        self._check_device(attrs.planes, attrs.material)
+        dev = attrs.planes.device
+        if out is None:
+            gb = GBuffer(torch.empty((N.NUM_PLANES, attrs.height, attrs.width), dtype=torch.float32, device=dev),
+                         opacity=torch.empty((attrs.height, attrs.width), dtype=torch.float32, device=dev))
+            coverage = torch.empty((attrs.height, attrs.width), dtype=torch.uint8, device=dev)
+        elif isinstance(out, GBuffer):
+            gb, coverage = out, None
+        else:
+            gb, coverage = out
+        self._check_device(gb.planes, gb.opacity, coverage)
+        if gb.height < attrs.height or gb.width < attrs.width:
+            raise ValueError("out is smaller than the attributes")
+        t = N.GBufferTargets()
+        ps = gb.planes.stride(0) * 4
+        t.planes[:] = [gb.planes.data_ptr() + i * ps for i in range(N.NUM_PLANES)]
+        t.opacity = None if gb.opacity is None else gb.opacity.data_ptr()
+        t.row_stride = int(gb.row_stride)
+        if coverage is not None:
+            if coverage.dtype != torch.uint8 or coverage.dim() != 2 or coverage.stride(1) != 1:
+                raise ValueError("coverage must be a (H, W) uint8 tensor with contiguous rows")
+            if coverage.shape[0] < attrs.height or coverage.shape[1] < attrs.width:
+                raise ValueError("coverage is smaller than the attributes")
+            t.coverage = coverage.data_ptr()
+            t.coverage_row_stride = coverage.stride(0)
+        a = attrs.to_c()
+        N.check(self.lib.pbr_resolve_materials(self._h, ctypes.byref(a), ctypes.byref(t), int(filter),
+                                               ctypes.c_void_p(_stream_handle(stream))),
+                "pbr_resolve_materials", self._h)
+        return gb, coverage
 
     def _check_device(self, *tensors) -> None:
         """Every tensor handed to the kernel must live on this context's device: a foreign pointer would be

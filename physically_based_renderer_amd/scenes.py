@@ -22,7 +22,7 @@ import numpy as np
 
 from . import _native as N
 from . import envmap
-from .renderer import GBuffer, PassConstants
+from .renderer import Attributes, GBuffer, Material, PassConstants
 
 ASSET_DIR = envmap.ASSET_DIR
 
@@ -191,6 +191,71 @@ def build_gbuffer(cfg: SceneConfig, device, row_begin: int = 0, row_end: Optiona
     dev = staging.to(device, non_blocking=True)
     torch.cuda.current_stream(device).synchronize()
     return GBuffer(dev)
+
+
+def _tile_materials(assets: Assets, textures: list) -> list:
+    """The seven *_1K sets (PBRApp.cpp:1270-1463) as textured materials: diffuse, specular, roughness and normal
+    maps, a metalness map where the set has one (else g_Metallic = 0). Their maps are appended to ``textures``."""
+    mats = []
+    for m in range(assets.mat_albedo.shape[0]):
+        base = len(textures)
+        textures += [assets.mat_albedo[m], assets.mat_specular[m], assets.mat_metallic[m], assets.mat_roughness[m],
+                     assets.mat_normal[m]]
+        has_metal = bool(assets.mat_has_metallic[m])
+        flags = (N.PBR_MAT_DIFFUSE_TEXTURE | N.PBR_MAT_SPECULAR_TEXTURE | N.PBR_MAT_ROUGHNESS_TEXTURE |
+                 N.PBR_MAT_NORMAL_TEXTURE | (N.PBR_MAT_METALLIC_TEXTURE if has_metal else 0))
+        mats.append(Material(metallic=0.0, flags=flags,
+                             tex=(base, base + 1, base + 2 if has_metal else -1, base + 3, base + 4, -1)))
+    return mats
+
+
+def scene_materials(cfg: SceneConfig):
+    """(materials, textures) for :meth:`ShadingContext.set_materials`, indexed by the material ids of
+    :func:`fill_attributes_host`: config 4's seven textured sets; the reference scene's 58 spheres (49 red
+    constants, PBRApp.cpp:964-973; rusted iron with its metallic and roughness maps; the copper constants; the
+    seven tiles, PBRApp.cpp:1016-1068)."""
+    assets = Assets.get()
+    textures: list = []
+    if cfg.kind == N.PBR_SCENE_PLANE_MATERIALS:
+        return _tile_materials(assets, textures), textures
+    if cfg.kind != N.PBR_SCENE_REFERENCE_SPHERES:
+        raise ValueError("scene_materials: config 4 and the reference scene only")
+    f = np.float32
+    mats = [Material(diffuse_albedo=(1.0, 0.0, 0.0), roughness=float(f(i % 7) / f(6.0)),
+                     metallic=float(f(1.0) - f(i // 7) / f(6.0))) for i in range(49)]
+    textures += [assets.rust_metallic, assets.rust_roughness]
+    mats.append(Material(diffuse_albedo=(0.5, 0.5, 0.5), tex=(-1, -1, 0, 1, -1, -1),
+                         flags=N.PBR_MAT_METALLIC_TEXTURE | N.PBR_MAT_ROUGHNESS_TEXTURE))
+    mats.append(Material(diffuse_albedo=(0.95, 0.64, 0.54), metallic=1.0, roughness=0.35))
+    mats += _tile_materials(assets, textures)
+    return mats, textures
+
+
+def fill_attributes_host(cfg: SceneConfig, row_begin: int = 0, row_end: Optional[int] = None, n_threads: int = 0):
+    """Host attribute planes (14, rows, width) float32 and material ids (rows, width) uint16 for rows
+    [row_begin, row_end) (pbr_attributes_fill): the interpolated VertexOut the G-buffer fill consumes in place."""
+    assets = Assets.get()
+    row_end = cfg.height if row_end is None else row_end
+    rows = row_end - row_begin
+    if rows < 0 or row_begin < 0 or row_end > cfg.height:
+        raise N.PbrError(-1, "pbr_attributes_fill", f"rows [{row_begin}, {row_end}) outside [0, {cfg.height})")
+    out = np.empty((N.NUM_ATTRIBUTE_PLANES, rows, cfg.width), np.float32)
+    mat = np.empty((rows, cfg.width), np.uint16)
+    if rows == 0:
+        return out, mat
+    ptrs = (ctypes.c_void_p * N.NUM_ATTRIBUTE_PLANES)(*[out[i].ctypes.data for i in range(N.NUM_ATTRIBUTE_PLANES)])
+    nt = n_threads or min(16, os.cpu_count() or 1)
+    d = _scene_desc(cfg, assets)
+    r = N.lib().pbr_attributes_fill(ctypes.byref(d), row_begin, row_end, ptrs, mat.ctypes.data, cfg.width, nt)
+    N.check(int(r), "pbr_attributes_fill")
+    return out, mat
+
+
+def build_attributes(cfg: SceneConfig, device, row_begin: int = 0, row_end: Optional[int] = None,
+                     n_threads: int = 0) -> Attributes:
+    """Fill rows of attributes on the host and upload them; :meth:`ShadingContext.resolve` makes the G-buffer."""
+    planes, mat = fill_attributes_host(cfg, row_begin, row_end, n_threads)
+    return Attributes.from_host(planes, mat, device)
 
 
 def env_map() -> np.ndarray:

@@ -2,6 +2,11 @@
 spheres, sky pass behind, fused RGBA8 back buffer) and write it as PNG.
 
     python tools/render_reference.py [--width 1920 --height 1080] [--overview] [--ibl] [--out path.png]
+                                     [--device-resolve [--filter point|linear]]
+
+--device-resolve fills only the interpolated attributes on the host and resolves the materials (texture fetches, F0,
+normal mapping: Default.hlsl:50-116) on the device (ShadingContext.resolve); its frame is not claimed equal to the
+host-fill frame at texel edges.
 """
 import argparse
 import os
@@ -14,7 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from physically_based_renderer_amd import _native as N, envmap, image_io  # noqa: E402
 from physically_based_renderer_amd import scenes as S  # noqa: E402
-from physically_based_renderer_amd.renderer import GBuffer, ShadingContext  # noqa: E402
+from physically_based_renderer_amd.renderer import Attributes, GBuffer, ShadingContext  # noqa: E402
 
 
 def main():
@@ -23,13 +28,19 @@ def main():
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--overview", action="store_true", help="back the camera off to show all 58 spheres")
     ap.add_argument("--ibl", action="store_true", help="diffuse IBL ambient (Chelsea_Stairs) instead of 0.03")
+    ap.add_argument("--device-resolve", action="store_true",
+                    help="host fills attributes only; materials resolve on the device (pbr_resolve_materials)")
+    ap.add_argument("--filter", choices=("point", "linear"), default="point", help="--device-resolve texture filter")
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "reference_scene.png"))
     a = ap.parse_args()
     cfg = S.REFERENCE_SCENE.with_size(a.width, a.height)
     if a.overview:
         cfg = cfg.with_camera(*S.OVERVIEW_CAMERA)
     t0 = time.perf_counter()
-    planes, cov = S.fill_gbuffer_host_coverage(cfg)
+    if a.device_resolve:
+        attrs_h, ids_h = S.fill_attributes_host(cfg)
+    else:
+        planes, cov = S.fill_gbuffer_host_coverage(cfg)
     t_fill = time.perf_counter() - t0
     pc = S.scene_pass(cfg)
     dev = torch.device("cuda", 0)
@@ -39,8 +50,14 @@ def main():
             ctx.set_env_map(S.env_map())
         ctx.set_pass(pc)
         ctx.set_sky_map(envmap.procedural_sky_rgba16(512, 256))
-        gb = GBuffer.from_host(planes, dev)
-        cv = torch.from_numpy(cov).to(dev)
+        if a.device_resolve:
+            ctx.set_materials(*S.scene_materials(cfg))
+            gb, cv = ctx.resolve(Attributes.from_host(attrs_h, ids_h, dev),
+                                 N.PBR_FILTER_LINEAR if a.filter == "linear" else N.PBR_FILTER_POINT)
+            cov = cv.cpu().numpy()
+        else:
+            gb = GBuffer.from_host(planes, dev)
+            cv = torch.from_numpy(cov).to(dev)
         img = ctx.shade_frame(gb, coverage=cv, fmt=N.PBR_OUTPUT_RGBA8_UNORM)
         t1 = time.perf_counter()
         while time.perf_counter() - t1 < 0.2:  # GPU clock ramp (bench.py --ramp-ms)

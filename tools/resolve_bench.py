@@ -1,0 +1,125 @@
+"""Time the device material resolve (pbr_resolve_materials) on config 4 against the only other route
+to the same device G-buffer and against the box's streaming rate, in one process on one GPU:
+
+  (a) the resolve kernel, point and linear filter: ms per frame (HIP events, median) and achieved GB/s on its
+      algorithmic bytes (14 attribute floats + a 2-byte id read, 15 planes + opacity + a coverage byte written:
+      123 B per pixel; texel fetches are not counted);
+  (b) the host route: pbr_gbuffer_fill on 16 threads + GBuffer.from_host (15 fp32 planes over PCIe), host clock
+      around work that ends in a device synchronise;
+  (c) a device-to-device copy moving (a)'s byte count (half read, half written): the streaming yardstick.
+
+    python tools/resolve_bench.py [--width 3840 --height 2160] [--steps 50] [--log profiles/r09/resolve_bench.log]
+
+The resolved planes are checked bit for bit against the host fill's before anything is timed.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from physically_based_renderer_amd import _native as N  # noqa: E402
+from physically_based_renderer_amd import scenes as S  # noqa: E402
+from physically_based_renderer_amd.renderer import GBuffer, ShadingContext  # noqa: E402
+
+BYTES_READ = 14 * 4 + 2
+BYTES_WRITTEN = 15 * 4 + 4 + 1
+
+
+def event_ms(fn, steps, ramp_s=0.2):
+    """Median / min / max of `steps` event-bracketed calls after a clock ramp of back-to-back calls."""
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < ramp_s:
+        for _ in range(8):
+            fn()
+        torch.cuda.synchronize()
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
+    for e0, e1 in ev:
+        e0.record()
+        fn()
+        e1.record()
+    torch.cuda.synchronize()
+    ms = sorted(e0.elapsed_time(e1) for e0, e1 in ev)
+    return {"median_ms": ms[len(ms) // 2], "min_ms": ms[0], "max_ms": ms[-1]}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--width", type=int, default=3840)
+    ap.add_argument("--height", type=int, default=2160)
+    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--host-reps", type=int, default=3)
+    ap.add_argument("--log", default=None, help="append the result lines to this file too")
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("resolve_bench: no GPU visible (timings are taken on the device only)")
+    problems = N.build_problems()
+    if problems:
+        sys.exit("resolve_bench: not the product build of this checkout: " + "; ".join(problems))
+    cfg = S.CONFIGS[4].with_size(a.width, a.height)
+    dev = torch.device("cuda", 0)
+    px = cfg.width * cfg.height
+    total = px * (BYTES_READ + BYTES_WRITTEN)
+    lines = []
+
+    def emit(d):
+        line = json.dumps(d)
+        print(line, flush=True)
+        lines.append(line)
+
+    emit({"tool": "resolve_bench", "workload": cfg.name, "width": cfg.width, "height": cfg.height,
+          "sources_sha": N.build_info()["sources_sha"], "device": torch.cuda.get_device_name(0),
+          "bytes_per_pixel": BYTES_READ + BYTES_WRITTEN, "algorithmic_bytes": total, "steps": a.steps})
+    with ShadingContext(0) as ctx:
+        # (b) the host route, timed first (also the reference planes of the equality check)
+        host_s = []
+        for _ in range(a.host_reps):
+            t0 = time.perf_counter()
+            planes, _ = S.fill_gbuffer_host(cfg, n_threads=16)
+            t1 = time.perf_counter()
+            gb_host = GBuffer.from_host(planes, dev)
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            host_s.append((t2 - t0, t1 - t0, t2 - t1))
+        host_s.sort()
+        b_ms = host_s[len(host_s) // 2][0] * 1e3
+        emit({"leg": "b_host_fill_plus_upload", "median_ms": b_ms, "fill_ms": host_s[len(host_s) // 2][1] * 1e3,
+              "upload_ms": host_s[len(host_s) // 2][2] * 1e3, "reps": a.host_reps,
+              "uploaded_bytes": int(planes.nbytes)})
+        ctx.set_materials(*S.scene_materials(cfg))
+        attrs = S.build_attributes(cfg, dev, n_threads=16)
+        res = {}
+        for name, filt in (("point", N.PBR_FILTER_POINT), ("linear", N.PBR_FILTER_LINEAR)):
+            out = ctx.resolve(attrs, filt)
+            torch.cuda.synchronize()
+            if filt == N.PBR_FILTER_POINT:  # the same G-buffer as the host route's, bit for bit
+                same = torch.equal(out[0].planes.view(torch.int32), gb_host.planes.view(torch.int32))
+                emit({"check": "resolved planes == host fill planes", "bit_identical": bool(same)})
+                if not same:
+                    sys.exit("resolve_bench: the device resolve differs from the host fill")
+            r = event_ms(lambda: ctx.resolve(attrs, filt, out=out), a.steps)
+            r.update(leg="a_resolve_" + name, gb_per_s=total / (r["median_ms"] * 1e-3) / 1e9)
+            res[name] = r
+            emit(r)
+        # (c) device-to-device copy moving the same bytes (half read, half written)
+        src = torch.empty(total // 2, dtype=torch.uint8, device=dev)
+        dst = torch.empty_like(src)
+        c = event_ms(lambda: dst.copy_(src), a.steps)
+        c.update(leg="c_d2d_copy", gb_per_s=total / (c["median_ms"] * 1e-3) / 1e9)
+        emit(c)
+        emit({"ratios": {"a_point_over_c": res["point"]["median_ms"] / c["median_ms"],
+                         "a_linear_over_c": res["linear"]["median_ms"] / c["median_ms"],
+                         "b_over_a_point": b_ms / res["point"]["median_ms"],
+                         "b_over_a_linear": b_ms / res["linear"]["median_ms"]}})
+    if a.log:
+        os.makedirs(os.path.dirname(os.path.abspath(a.log)), exist_ok=True)
+        with open(a.log, "a") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
