@@ -339,6 +339,91 @@ typedef struct pbr_gbuffer_targets {
 int pbr_resolve_materials(pbr_context* ctx, const pbr_attributes_soa* attrs, const pbr_gbuffer_targets* targets,
                           int32_t filter, void* stream);
 
+/* ---- Device rasteriser: indexed triangle meshes -> interpolated attributes ----------------------
+ * VS (Default.hlsl:22-45) and the fixed-function rasteriser behind DrawIndexedInstanced (PBRApp.cpp:1133) under the
+ * reference's PSO state (CD3DX12_RASTERIZER_DESC(D3D12_DEFAULT), CD3DX12_DEPTH_STENCIL_DESC(D3D12_DEFAULT),
+ * PBRApp.cpp:793-795; CULL_MODE_NONE for the transparent, alpha-tested and sky PSOs, :843-859), on the device: indexed
+ * triangle lists in, the planes of a pbr_attributes_soa out, which pbr_resolve_materials consumes (which
+ * fixes the semantics operation by operation: top-left rule on an 8-bit subpixel grid, one sample per pixel, depth
+ * test LESS against a buffer cleared to 1, perspective-correct attributes; no clipping against w = 0). Additive like
+ * the resolve: PBR_ABI_VERSION stays 9, detect by symbol. */
+
+/* One mesh in HOST memory: vertices in the reference's `Vertex` order (FrameResource.h:46-52), 14 floats each (Pos 3,
+ * Normal 3, Tangent 3, Bitangent 3, TexCoord 2), and a triangle list of 32-bit indices. */
+typedef struct pbr_mesh_desc {
+    const float* vertices;   /* n_vertices * 14 floats */
+    const uint32_t* indices; /* n_indices, each < n_vertices */
+    int32_t n_vertices;
+    int32_t n_indices;
+} pbr_mesh_desc;
+
+/* Uploads the meshes pbr_rasterize draws from (replaces BuildShapeGeometry's vertex / index buffer uploads). Same
+ * rules as pbr_set_materials: the host data may be reused on return, the previous set is released in stream order
+ * after the queued rasterisations that read it (on any stream), call it outside a graph capture.
+ * PBR_ERR_INVALID_ARGUMENT: a null pointer (of a non-empty array), a negative count, an index >= n_vertices (the
+ * indices are validated here, once, on the host). */
+int pbr_set_meshes(pbr_context* ctx, const pbr_mesh_desc* meshes, int32_t n_meshes, void* stream);
+
+/* One render item (RenderItem + DrawIndexedInstanced, PBRApp.cpp:1103-1134). Matrices are row-major and multiply a
+ * row vector from the right, as mul(v, M) does in Default.hlsl:27-42. */
+typedef struct pbr_draw {
+    int32_t mesh;        /* index into the set of pbr_set_meshes */
+    int32_t first_index; /* StartIndexLocation */
+    int32_t index_count; /* IndexCount: a multiple of 3, first_index + index_count <= the mesh's n_indices */
+    uint16_t material;   /* written to the material plane where the draw is visible */
+    uint16_t cull;       /* 0 = back faces culled (D3D12_DEFAULT), 1 = none */
+    float world[16];         /* g_World */
+    float tex_transform[16]; /* g_TexTransform */
+    float mat_transform[16]; /* g_MatTransform */
+} pbr_draw;
+
+typedef struct pbr_raster_view {
+    float view_proj[16]; /* g_ViewProj; depth 0..1 */
+    int32_t width;       /* the full frame: pixel values depend on the global (x, y) only */
+    int32_t height;
+    int32_t row_begin;   /* the targets hold rows [row_begin, row_end) of the frame */
+    int32_t row_end;
+    /* Background pixels (no fragment) get the layout pbr_attributes_fill gives them: with sx = (2x+1)/width - 1 and
+     * sy = 1 - (2y+1)/height, d = normalize(bg_forward + sx * bg_right + sy * bg_up) in the normal planes and
+     * eye + 100 d in the position planes (bg_right and bg_up carry the tangent of the half field of view). */
+    float eye[3];
+    float bg_right[3];
+    float bg_up[3];
+    float bg_forward[3];
+} pbr_raster_view;
+
+/* Where the rasteriser writes, DEVICE memory: the 14 planes of a pbr_attributes_soa in its order, the material id
+ * plane, and optionally the depth plane (z of the visible fragment, 1 for the background). One row stride; plane
+ * pointers point at row `row_begin`. */
+typedef struct pbr_raster_targets {
+    float* planes[14];
+    uint16_t* material;
+    float* depth;       /* may be NULL */
+    int64_t row_stride; /* elements; >= width */
+} pbr_raster_targets;
+
+/* Rasterises `draws` in order into `targets`, asynchronously on `stream`; `draws` may be reused on return. Every pixel
+ * of the band is written. The result is independent of execution order (nearest z wins, equal z goes to the earlier
+ * triangle in draw order then index order) and of the band: a band equals the same rows of the full frame. Not a
+ * shading pass: pbr_last_pass_stats / _cull_stats / _kernel are unchanged by it.
+ * PBR_ERR_NOT_READY before pbr_set_meshes; PBR_ERR_INVALID_ARGUMENT for a bad mesh id or index range, an index_count
+ * that is no multiple of 3, a cull mode other than 0 or 1, more than 2^32 - 2 triangles in the call. */
+int pbr_rasterize(pbr_context* ctx, const pbr_draw* draws, int32_t n_draws, const pbr_raster_view* view,
+                  const pbr_raster_targets* targets, void* stream);
+
+typedef struct pbr_raster_stats {
+    int64_t triangles;          /* submitted */
+    int64_t backface_culled;    /* signed area < 0 under cull 0 */
+    int64_t zero_area;          /* signed area == 0 on the subpixel grid */
+    int64_t skipped_near;       /* a vertex whose w is not > 0: not drawn (no clipping against w = 0) */
+    int64_t skipped_guard_band; /* a vertex beyond +-2^23 subpixels, or not finite: not drawn */
+    int64_t fragments;          /* (triangle, pixel) pairs that passed coverage and 0 <= z < 1 */
+} pbr_raster_stats;
+
+/* The counters of the last pbr_rasterize on `stream` (synchronises `stream`, like pbr_last_cull_stats); zeros when
+ * the context has not rasterised on that stream. */
+int pbr_last_raster_stats(pbr_context* ctx, pbr_raster_stats* out, void* stream);
+
 /* ---- Host G-buffer fill (replaces the VS + rasteriser front-end, Default.hlsl:22-45) ---------- */
 
 typedef enum pbr_scene_kind {

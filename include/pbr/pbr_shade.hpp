@@ -375,6 +375,38 @@ class ShadingContext {
         Check(pbr_resolve_materials(ctx_, &attrs, &t, filter, stream), "pbr_resolve_materials");
     }
 
+    // The meshes Rasterize draws from (BuildShapeGeometry's vertex / index buffer uploads): host data, reusable on
+    // return.
+    void SetMeshes(const std::vector<pbr_mesh_desc>& meshes, hipStream_t stream = nullptr) {
+        Check(pbr_set_meshes(ctx_, meshes.data(), static_cast<int32_t>(meshes.size()), stream), "pbr_set_meshes");
+    }
+    // VS + the rasteriser (Default.hlsl:22-45, DrawIndexedInstanced): `draws` in order under `view`
+    // into rows [view.row_begin, view.row_end) of `attrs` (a full-frame buffer), with an optional depth plane of
+    // attrs' row stride holding the same rows.
+    void Rasterize(const std::vector<pbr_draw>& draws, const pbr_raster_view& view, DeviceAttributes& attrs,
+                   float* depth = nullptr, hipStream_t stream = nullptr) {
+        const pbr_attributes_soa band = attrs.Band(view.row_begin, view.row_end);
+        pbr_raster_targets t;
+        std::memset(&t, 0, sizeof t);
+        for (int k = 0; k < 3; ++k) {
+            t.planes[0 + k] = const_cast<float*>(band.pos_w[k]);
+            t.planes[3 + k] = const_cast<float*>(band.normal_w[k]);
+            t.planes[6 + k] = const_cast<float*>(band.tangent_w[k]);
+            t.planes[9 + k] = const_cast<float*>(band.bitangent_w[k]);
+        }
+        t.planes[12] = const_cast<float*>(band.tex_coord[0]);
+        t.planes[13] = const_cast<float*>(band.tex_coord[1]);
+        t.material = const_cast<uint16_t*>(band.material);
+        t.depth = depth;
+        t.row_stride = band.row_stride;
+        Check(pbr_rasterize(ctx_, draws.data(), static_cast<int32_t>(draws.size()), &view, &t, stream), "pbr_rasterize");
+    }
+    pbr_raster_stats LastRasterStats(hipStream_t stream = nullptr) {
+        pbr_raster_stats s;
+        Check(pbr_last_raster_stats(ctx_, &s, stream), "pbr_last_raster_stats");
+        return s;
+    }
+
     pbr_pass_stats LastPassStats(hipStream_t stream = nullptr) {
         pbr_pass_stats s;
         Check(pbr_last_pass_stats(ctx_, &s, stream), "pbr_last_pass_stats");

@@ -191,6 +191,64 @@ class GBufferTargets(ctypes.Structure):
     ]
 
 
+class MeshDesc(ctypes.Structure):
+    """pbr_mesh_desc: HOST vertices (14 floats each: Pos, Normal, Tangent, Bitangent, TexCoord) and uint32 indices."""
+    _fields_ = [
+        ("vertices", ctypes.c_void_p),
+        ("indices", ctypes.c_void_p),
+        ("n_vertices", ctypes.c_int32),
+        ("n_indices", ctypes.c_int32),
+    ]
+
+
+class DrawDesc(ctypes.Structure):
+    """pbr_draw: one render item; row-major matrices that multiply a row vector, mul(v, M)."""
+    _fields_ = [
+        ("mesh", ctypes.c_int32),
+        ("first_index", ctypes.c_int32),
+        ("index_count", ctypes.c_int32),
+        ("material", ctypes.c_uint16),
+        ("cull", ctypes.c_uint16),
+        ("world", ctypes.c_float * 16),
+        ("tex_transform", ctypes.c_float * 16),
+        ("mat_transform", ctypes.c_float * 16),
+    ]
+
+
+class RasterView(ctypes.Structure):
+    _fields_ = [
+        ("view_proj", ctypes.c_float * 16),
+        ("width", ctypes.c_int32),
+        ("height", ctypes.c_int32),
+        ("row_begin", ctypes.c_int32),
+        ("row_end", ctypes.c_int32),
+        ("eye", ctypes.c_float * 3),
+        ("bg_right", ctypes.c_float * 3),
+        ("bg_up", ctypes.c_float * 3),
+        ("bg_forward", ctypes.c_float * 3),
+    ]
+
+
+class RasterTargets(ctypes.Structure):
+    _fields_ = [
+        ("planes", ctypes.c_void_p * 14),
+        ("material", ctypes.c_void_p),
+        ("depth", ctypes.c_void_p),
+        ("row_stride", ctypes.c_int64),
+    ]
+
+
+class RasterStats(ctypes.Structure):
+    _fields_ = [
+        ("triangles", ctypes.c_int64),
+        ("backface_culled", ctypes.c_int64),
+        ("zero_area", ctypes.c_int64),
+        ("skipped_near", ctypes.c_int64),
+        ("skipped_guard_band", ctypes.c_int64),
+        ("fragments", ctypes.c_int64),
+    ]
+
+
 class PassStats(ctypes.Structure):
     """pbr_pass_stats: statistics of the last shading pass."""
     _fields_ = [
@@ -242,6 +300,10 @@ SIGNATURES = {
                                          ctypes.POINTER(TextureDesc), ctypes.c_int32, ctypes.c_void_p]),
     "pbr_resolve_materials": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(AttributesSoA),
                                              ctypes.POINTER(GBufferTargets), ctypes.c_int32, ctypes.c_void_p]),
+    "pbr_set_meshes": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(MeshDesc), ctypes.c_int32, ctypes.c_void_p]),
+    "pbr_rasterize": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(DrawDesc), ctypes.c_int32,
+                                     ctypes.POINTER(RasterView), ctypes.POINTER(RasterTargets), ctypes.c_void_p]),
+    "pbr_last_raster_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(RasterStats), ctypes.c_void_p]),
     "pbr_attributes_fill": (ctypes.c_int64, [ctypes.POINTER(SceneDesc), ctypes.c_int32, ctypes.c_int32,
                                              ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.c_int64,
                                              ctypes.c_int32]),

@@ -111,7 +111,33 @@ struct StreamState {
     int64_t tiles = 0, slots = 0;
     bool culled = false;
     std::string kernel;  // the last pass's kernel (pbr_last_pass_kernel)
+    // pbr_rasterize on this stream (raster.h): its device scratch -- counters, the draw table, the transformed vertex
+    // records, the large-triangle list, the visibility words -- grown in stream order on this stream, and the pinned
+    // staging of the draw table with the event of its last upload. A stream has its own, so rasterisations queued on
+    // two streams never share scratch.
+    struct Raster {
+        char* d = nullptr;
+        size_t capacity = 0;
+        char* h = nullptr;  // pinned
+        size_t h_capacity = 0;
+        hipEvent_t staged = nullptr;
+        bool staged_pending = false;
+        unsigned long long* d_counters = nullptr;  // inside d
+        int64_t triangles = 0;
+        bool ran = false;
+    };
+    Raster raster;
 };
+
+// After the stream's work is complete (a device synchronisation): give back what a StreamState owns.
+static void release_stream_state(StreamState& st) {
+    if (st.last_pass) (void)hipEventDestroy(st.last_pass);
+    if (st.d_stats) (void)hipFree(st.d_stats);
+    if (st.raster.staged) (void)hipEventDestroy(st.raster.staged);
+    if (st.raster.h) (void)hipHostFree(st.raster.h);
+    if (st.raster.d) (void)hipFreeAsync(st.raster.d, nullptr);
+    st = StreamState{};
+}
 
 struct Resource {
     std::vector<int> readers;  // StreamState indices that launched a pass reading it since the last write
@@ -159,6 +185,20 @@ struct pbr_context {
         Resource use;
     };
     Materials mats;
+    // The meshes pbr_rasterize draws from (pbr_set_meshes): every mesh's vertices in one buffer, every index in
+    // another, replaced as a whole; the placement of each mesh stays on the host.
+    struct MeshPlace {
+        uint32_t vtx_base, n_vertices, idx_base, n_indices;
+    };
+    struct Meshes {
+        float* d_vertices = nullptr;
+        uint32_t* d_indices = nullptr;
+        int64_t n_vertices = 0, n_indices = 0;
+        std::vector<MeshPlace> place;
+        bool set = false;
+        Resource use;
+    };
+    Meshes meshes;
     // Current pass.
     pbr::PassArgs pass{};
     int ambient_mode = 0;
@@ -264,8 +304,7 @@ int stream_index(pbr_context* ctx, hipStream_t s, hipError_t& e) {
                     keep.push_back(std::move(st));
                     continue;
                 }
-                if (st.last_pass) (void)hipEventDestroy(st.last_pass);
-                if (st.d_stats) (void)hipFree(st.d_stats);
+                release_stream_state(st);
             }
             ctx->last_stream = keep.empty() ? -1 : 0;
             ctx->streams = std::move(keep);
@@ -340,6 +379,8 @@ void forget_readers(pbr_context* ctx) {
     }
     ctx->mats.use.readers.clear();
     ctx->mats.use.writer = -1;
+    ctx->meshes.use.readers.clear();
+    ctx->meshes.use.writer = -1;
 }
 
 }  // namespace
@@ -432,10 +473,10 @@ int pbr_context_destroy(pbr_context* ctx) {
         if (ctx->mats.d_table) (void)hipFreeAsync(ctx->mats.d_table, nullptr);
         if (ctx->mats.d_texels) (void)hipFreeAsync(ctx->mats.d_texels, nullptr);
         if (ctx->mats.use.written) (void)hipEventDestroy(ctx->mats.use.written);
-        for (StreamState& st : ctx->streams) {
-            if (st.last_pass) (void)hipEventDestroy(st.last_pass);
-            if (st.d_stats) (void)hipFree(st.d_stats);
-        }
+        if (ctx->meshes.d_vertices) (void)hipFreeAsync(ctx->meshes.d_vertices, nullptr);
+        if (ctx->meshes.d_indices) (void)hipFreeAsync(ctx->meshes.d_indices, nullptr);
+        if (ctx->meshes.use.written) (void)hipEventDestroy(ctx->meshes.use.written);
+        for (StreamState& st : ctx->streams) release_stream_state(st);
         (void)hipDeviceSynchronize();
     }
     delete ctx;
@@ -942,6 +983,299 @@ int pbr_resolve_materials(pbr_context* ctx, const pbr_attributes_soa* at, const 
 
 }  // extern "C"
 
+// ---- Rasteriser (VS + the fixed-function rasteriser on the device; raster.h) --------------------------
+
+namespace {
+
+constexpr int32_t kRasterMaxSide = 32768;  // frame width and height: keeps every block and pixel count inside 32 bits
+
+size_t align_up(size_t n, size_t a) { return (n + a - 1) / a * a; }
+
+// The calling stream's pinned staging with room for `bytes`, free to be written: waits (on the host) for the upload
+// that last read it.
+hipError_t raster_staging(StreamState::Raster& r, size_t bytes) {
+    hipError_t e = hipSuccess;
+    if (r.staged_pending) {
+        e = hipEventSynchronize(r.staged);
+        if (e != hipSuccess) return e;
+        r.staged_pending = false;
+    }
+    if (!r.staged) {
+        e = hipEventCreateWithFlags(&r.staged, hipEventDisableTiming);
+        if (e != hipSuccess) return e;
+    }
+    if (bytes > r.h_capacity) {
+        if (r.h) (void)hipHostFree(r.h);
+        r.h = nullptr;
+        r.h_capacity = 0;
+        const size_t cap = align_up(bytes + bytes / 2, 4096);
+        e = hipHostMalloc(reinterpret_cast<void**>(&r.h), cap, hipHostMallocDefault);
+        if (e != hipSuccess) return e;
+        r.h_capacity = cap;
+    }
+    return hipSuccess;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pbr_set_meshes(pbr_context* ctx, const pbr_mesh_desc* meshes, int32_t n_meshes, void* stream) {
+    if (!ctx || n_meshes < 0 || (n_meshes > 0 && !meshes)) return PBR_ERR_INVALID_ARGUMENT;
+    std::vector<pbr_context::MeshPlace> place((size_t)n_meshes);
+    int64_t nv = 0, ni = 0;
+    for (int32_t i = 0; i < n_meshes; ++i) {
+        const pbr_mesh_desc& m = meshes[i];
+        if (m.n_vertices < 0 || m.n_indices < 0) return PBR_ERR_INVALID_ARGUMENT;
+        if ((m.n_vertices > 0 && !m.vertices) || (m.n_indices > 0 && !m.indices)) return PBR_ERR_INVALID_ARGUMENT;
+        for (int32_t k = 0; k < m.n_indices; ++k)
+            if (m.indices[k] >= (uint32_t)m.n_vertices) return PBR_ERR_INVALID_ARGUMENT;
+        place[(size_t)i] = pbr_context::MeshPlace{(uint32_t)nv, (uint32_t)m.n_vertices, (uint32_t)ni, (uint32_t)m.n_indices};
+        nv += m.n_vertices;
+        ni += m.n_indices;
+        if (nv > (1ll << 27) || ni > (1ll << 31)) return PBR_ERR_INVALID_ARGUMENT;  // 7.5 GB of vertices, 8 GB of indices
+    }
+    std::vector<float> vertices((size_t)(nv > 0 ? nv * 14 : 1), 0.0f);
+    std::vector<uint32_t> indices((size_t)(ni > 0 ? ni : 1), 0u);
+    for (int32_t i = 0; i < n_meshes; ++i) {
+        const pbr_mesh_desc& m = meshes[i];
+        if (m.n_vertices > 0)
+            std::memcpy(vertices.data() + (size_t)place[(size_t)i].vtx_base * 14, m.vertices,
+                        sizeof(float) * 14 * (size_t)m.n_vertices);
+        if (m.n_indices > 0)
+            std::memcpy(indices.data() + place[(size_t)i].idx_base, m.indices, sizeof(uint32_t) * (size_t)m.n_indices);
+    }
+
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DeviceGuard g(ctx->device);
+    if (!g.ok) return PBR_ERR_NO_DEVICE;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipError_t e = hipSuccess;
+    const int si = stream_index(ctx, s, e);
+    if (si < 0) return fail_hip(ctx, e, "pbr_set_meshes stream");
+    pbr_context::Meshes& ms = ctx->meshes;
+    // The old buffers may still be read by queued rasterisations: released after them, in stream order.
+    e = free_after_readers(ctx, ms.use, ms.d_vertices, s, si);
+    if (e == hipSuccess && ms.d_indices) e = hipFreeAsync(ms.d_indices, s);
+    if (e != hipSuccess) return fail_hip(ctx, e, "pbr_set_meshes release");
+    ms.d_vertices = nullptr;
+    ms.d_indices = nullptr;
+    ms.set = false;
+    e = hipMallocAsync(reinterpret_cast<void**>(&ms.d_vertices), sizeof(float) * vertices.size(), s);
+    if (e == hipSuccess) e = hipMallocAsync(reinterpret_cast<void**>(&ms.d_indices), sizeof(uint32_t) * indices.size(), s);
+    if (e != hipSuccess) return fail_hip(ctx, e, "pbr_set_meshes hipMalloc");
+    e = hipMemcpyAsync(ms.d_vertices, vertices.data(), sizeof(float) * vertices.size(), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(ms.d_indices, indices.data(), sizeof(uint32_t) * indices.size(), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);  // the staging copies above are released on return
+    if (e != hipSuccess) return fail_hip(ctx, e, "pbr_set_meshes copy");
+    ms.use.writer = -1;  // complete: later rasterisations on any stream see the new set
+    ms.n_vertices = nv;
+    ms.n_indices = ni;
+    ms.place = std::move(place);
+    ms.set = true;
+    return PBR_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// pbr_rasterize. `marks` (development, pbr_debug_rasterize_timed): six events recorded around the five stages --
+// clears and table upload, vertex transform, setup with the small triangles' coverage, large triangles, resolve.
+int rasterize_impl(pbr_context* ctx, const pbr_draw* draws, int32_t n_draws, const pbr_raster_view* view,
+                   const pbr_raster_targets* tg, void* stream, hipEvent_t* marks) {
+    if (!ctx || !view || !tg || n_draws < 0 || (n_draws > 0 && !draws)) return PBR_ERR_INVALID_ARGUMENT;
+    if (view->width < 0 || view->height < 0 || view->width > kRasterMaxSide || view->height > kRasterMaxSide)
+        return PBR_ERR_INVALID_ARGUMENT;
+    if (view->row_begin < 0 || view->row_begin > view->row_end || view->row_end > view->height)
+        return PBR_ERR_INVALID_ARGUMENT;
+    if (tg->row_stride < view->width) return PBR_ERR_INVALID_ARGUMENT;
+    for (int32_t i = 0; i < n_draws; ++i) {
+        const pbr_draw& d = draws[i];
+        if (d.mesh < 0 || d.first_index < 0 || d.index_count < 0 || d.index_count % 3 != 0 || d.cull > 1)
+            return PBR_ERR_INVALID_ARGUMENT;
+    }
+    pbr::RasterArgs a{};
+    a.vec = (tg->row_stride % 2) == 0;
+    for (int i = 0; i < 14; ++i) {
+        if (!tg->planes[i] || !aligned(tg->planes[i], 4)) return PBR_ERR_INVALID_ARGUMENT;
+        a.plane[i] = tg->planes[i];
+        a.vec = a.vec && aligned(tg->planes[i], 8);
+    }
+    if (!tg->material || !aligned(tg->material, 2)) return PBR_ERR_INVALID_ARGUMENT;
+    if (tg->depth && !aligned(tg->depth, 4)) return PBR_ERR_INVALID_ARGUMENT;
+    a.material = tg->material;
+    a.depth = tg->depth;
+    a.vec = a.vec && aligned(tg->material, 4) && aligned(tg->depth, 8);
+    a.stride = tg->row_stride;
+    a.width = view->width;
+    a.height = view->height;
+    a.row_begin = view->row_begin;
+    a.row_end = view->row_end;
+    std::memcpy(a.view_proj, view->view_proj, sizeof(a.view_proj));
+    for (int c = 0; c < 3; ++c)
+        a.eye[c] = view->eye[c], a.right[c] = view->bg_right[c], a.up[c] = view->bg_up[c], a.fwd[c] = view->bg_forward[c];
+
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    const pbr_context::Meshes& ms = ctx->meshes;
+    if (!ms.set) return PBR_ERR_NOT_READY;
+    uint64_t n_tris = 0, n_records = 0;
+    for (int32_t i = 0; i < n_draws; ++i) {
+        const pbr_draw& d = draws[i];
+        if ((size_t)d.mesh >= ms.place.size()) return PBR_ERR_INVALID_ARGUMENT;
+        const pbr_context::MeshPlace& mp = ms.place[(size_t)d.mesh];
+        if ((uint64_t)d.first_index + (uint64_t)d.index_count > (uint64_t)mp.n_indices) return PBR_ERR_INVALID_ARGUMENT;
+        n_tris += (uint64_t)d.index_count / 3u;
+        n_records += mp.n_vertices;
+    }
+    if (n_tris > 0xFFFFFFFEull || n_records > 0x7FFFFFFFull) return PBR_ERR_INVALID_ARGUMENT;
+    const int band_h = view->row_end - view->row_begin;
+    if (view->width == 0 || band_h == 0) return PBR_OK;  // an empty band: nothing is read or written
+
+    DeviceGuard g(ctx->device);
+    if (!g.ok) return PBR_ERR_NO_DEVICE;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipError_t e = hipSuccess;
+    const int si = stream_index(ctx, s, e);
+    if (si < 0) return fail_hip(ctx, e, "pbr_rasterize stream");
+    StreamState::Raster& rs = ctx->streams[si].raster;
+
+    // The draw table: the records, then the triangle and vertex-record prefixes.
+    const size_t nd = (size_t)n_draws;
+    const size_t table_bytes = sizeof(pbr::RasterDraw) * nd + sizeof(uint32_t) * 2 * (nd + 1);
+    e = raster_staging(rs, table_bytes);
+    if (e != hipSuccess) return fail_hip(ctx, e, "pbr_rasterize staging");
+    pbr::RasterDraw* h_draws = reinterpret_cast<pbr::RasterDraw*>(rs.h);
+    uint32_t* h_tri = reinterpret_cast<uint32_t*>(rs.h + sizeof(pbr::RasterDraw) * nd);
+    uint32_t* h_rec = h_tri + (nd + 1);
+    uint32_t tri = 0, rec = 0;
+    for (size_t i = 0; i < nd; ++i) {
+        const pbr_draw& d = draws[i];
+        const pbr_context::MeshPlace& mp = ms.place[(size_t)d.mesh];
+        pbr::RasterDraw& r = h_draws[i];
+        std::memcpy(r.world, d.world, sizeof(r.world));
+        std::memcpy(r.tex, d.tex_transform, sizeof(r.tex));
+        std::memcpy(r.mat, d.mat_transform, sizeof(r.mat));
+        r.vtx_src = mp.vtx_base;
+        r.idx_src = mp.idx_base + (uint32_t)d.first_index;
+        r.rec_base = rec;
+        r.n_vertices = mp.n_vertices;
+        r.material = d.material;
+        r.cull = d.cull;
+        r.pad[0] = r.pad[1] = 0u;
+        h_tri[i] = tri;
+        h_rec[i] = rec;
+        tri += (uint32_t)d.index_count / 3u;
+        rec += mp.n_vertices;
+    }
+    h_tri[nd] = tri;
+    h_rec[nd] = rec;
+
+    // Device scratch of this stream: counters | draw table | vertex records | large list | visibility words.
+    const size_t off_table = 256;
+    const size_t off_records = off_table + align_up(table_bytes, 256);
+    const size_t off_large = off_records + align_up(sizeof(pbr::RasterVertex) * (size_t)n_records, 256);
+    const size_t off_vis = off_large + align_up(sizeof(uint2) * (size_t)n_tris, 256);
+    const size_t vis_bytes = sizeof(unsigned long long) * (size_t)band_h * (size_t)view->width;
+    const size_t need = off_vis + vis_bytes;
+    if (need > rs.capacity) {  // grown in stream order: the stream's earlier rasterisations finish with the old block
+        if (rs.d) {
+            e = hipFreeAsync(rs.d, s);
+            if (e != hipSuccess) return fail_hip(ctx, e, "pbr_rasterize release");
+        }
+        rs.d = nullptr;
+        rs.capacity = 0;
+        e = hipMallocAsync(reinterpret_cast<void**>(&rs.d), need, s);
+        if (e != hipSuccess) return fail_hip(ctx, e, "pbr_rasterize hipMalloc");
+        rs.capacity = need;
+    }
+    rs.d_counters = reinterpret_cast<unsigned long long*>(rs.d);
+    a.counters = rs.d_counters;
+    a.draws = reinterpret_cast<const pbr::RasterDraw*>(rs.d + off_table);
+    a.tri_prefix = reinterpret_cast<const uint32_t*>(rs.d + off_table + sizeof(pbr::RasterDraw) * nd);
+    a.rec_prefix = a.tri_prefix + (nd + 1);
+    a.records = reinterpret_cast<pbr::RasterVertex*>(rs.d + off_records);
+    a.large = reinterpret_cast<uint2*>(rs.d + off_large);
+    a.vis = reinterpret_cast<unsigned long long*>(rs.d + off_vis);
+    a.n_draws = n_draws;
+    a.n_tris = (uint32_t)n_tris;
+    a.n_records = (uint32_t)n_records;
+    a.vertices = ms.d_vertices;
+    a.indices = ms.d_indices;
+    a.n_src_vertices = ms.n_vertices;
+    a.n_src_indices = ms.n_indices;
+
+    e = before_read(ctx->meshes.use, s, si);
+    if (e != hipSuccess) return fail_hip(ctx, e, "pbr_rasterize order");
+    auto mark = [&](int i) { return marks ? hipEventRecord(marks[i], s) : hipSuccess; };
+    (void)mark(0);
+    e = hipMemsetAsync(rs.d, 0, sizeof(unsigned long long) * pbr::kRasterCounters, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(rs.d + off_table, rs.h, table_bytes, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipEventRecord(rs.staged, s);
+    if (e != hipSuccess) return fail_hip(ctx, e, "pbr_rasterize upload");
+    rs.staged_pending = true;
+    e = hipMemsetAsync(a.vis, 0xFF, vis_bytes, s);
+    if (e != hipSuccess) return fail_hip(ctx, e, "pbr_rasterize clear");
+    (void)mark(1);
+    e = pbr::launch_raster_vertices(a, s);
+    if (e != hipSuccess) return fail_hip(ctx, e, "raster_vertex_kernel launch", PBR_ERR_LAUNCH);
+    (void)mark(2);
+    e = pbr::launch_raster_setup(a, s);
+    if (e != hipSuccess) return fail_hip(ctx, e, "raster_setup_kernel launch", PBR_ERR_LAUNCH);
+    (void)mark(3);
+    e = pbr::launch_raster_large(a, s);
+    if (e != hipSuccess) return fail_hip(ctx, e, "raster_large_kernel launch", PBR_ERR_LAUNCH);
+    (void)mark(4);
+    e = pbr::launch_raster_resolve(a, s);
+    if (e != hipSuccess) return fail_hip(ctx, e, "raster_resolve_kernel launch", PBR_ERR_LAUNCH);
+    (void)mark(5);
+    rs.triangles = (int64_t)n_tris;
+    rs.ran = true;
+    // Not a shading pass: the stream's statistics record and kernel name stay; only the event that orders a later
+    // pbr_set_meshes after this read is recorded.
+    if (ctx->streams.size() > 1) {
+        e = hipEventRecord(ctx->streams[si].last_pass, s);
+        if (e != hipSuccess) return fail_hip(ctx, e, "pbr_rasterize record");
+    }
+    return PBR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pbr_rasterize(pbr_context* ctx, const pbr_draw* draws, int32_t n_draws, const pbr_raster_view* view,
+                  const pbr_raster_targets* targets, void* stream) {
+    return rasterize_impl(ctx, draws, n_draws, view, targets, stream, nullptr);
+}
+
+int pbr_last_raster_stats(pbr_context* ctx, pbr_raster_stats* out, void* stream) {
+    if (!ctx || !out) return PBR_ERR_INVALID_ARGUMENT;
+    *out = pbr_raster_stats{};
+    DeviceGuard g(ctx->device);
+    if (!g.ok) return PBR_ERR_NO_DEVICE;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const StreamState* st = nullptr;
+    for (const StreamState& c : ctx->streams)
+        if (c.stream == s && c.raster.ran) st = &c;
+    if (!st) return PBR_OK;
+    unsigned long long h[pbr::kRasterCounters] = {};
+    hipError_t e = hipMemcpyAsync(h, st->raster.d_counters, sizeof(h), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return fail_hip(ctx, e, "pbr_last_raster_stats");
+    out->triangles = st->raster.triangles;
+    out->backface_culled = (int64_t)h[pbr::kRasterCulled];
+    out->zero_area = (int64_t)h[pbr::kRasterZeroArea];
+    out->skipped_near = (int64_t)h[pbr::kRasterNear];
+    out->skipped_guard_band = (int64_t)h[pbr::kRasterGuard];
+    out->fragments = (int64_t)h[pbr::kRasterFragments];
+    return PBR_OK;
+}
+
+}  // extern "C"
+
 namespace {
 
 // Sum the statistics records of the last pass on `stream` (or, if the context never launched on that stream,
@@ -1028,6 +1362,29 @@ int pbr_debug_bounds(pbr_context* ctx, uint32_t* flags, int reset) {
 }
 
 }  // extern "C"
+
+// Development (tools/raster_bench.py; not in the public header): one pbr_rasterize with HIP events between its stages;
+// synchronises `stream` and writes the milliseconds of the clears and table upload, the vertex transform, the setup
+// with the small triangles' coverage, the large triangles' coverage and the per-pixel resolve into ms5.
+extern "C" int pbr_debug_rasterize_timed(pbr_context* ctx, const pbr_draw* draws, int32_t n_draws,
+                                         const pbr_raster_view* view, const pbr_raster_targets* targets, void* stream,
+                                         float* ms5) {
+    if (!ctx || !ms5) return PBR_ERR_INVALID_ARGUMENT;
+    DeviceGuard g(ctx->device);
+    if (!g.ok) return PBR_ERR_NO_DEVICE;
+    hipEvent_t ev[6] = {};
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < 6 && e == hipSuccess; ++i) e = hipEventCreate(&ev[i]);
+    int rc = e == hipSuccess ? rasterize_impl(ctx, draws, n_draws, view, targets, stream, ev) : PBR_ERR_HIP;
+    if (rc == PBR_OK && hipStreamSynchronize(static_cast<hipStream_t>(stream)) != hipSuccess) rc = PBR_ERR_HIP;
+    for (int i = 0; i < 5; ++i) {
+        ms5[i] = 0.0f;
+        if (rc == PBR_OK && hipEventElapsedTime(&ms5[i], ev[i], ev[i + 1]) != hipSuccess) rc = PBR_ERR_HIP;
+    }
+    for (hipEvent_t x : ev)
+        if (x) (void)hipEventDestroy(x);
+    return rc;
+}
 
 // Development: the balanced pass's per-phase clock sums of a PBR_BAL_PROFILE build (not in the public header).
 extern "C" int pbr_debug_bal_profile(unsigned long long* out8, int reset) {

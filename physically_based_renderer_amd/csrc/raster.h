@@ -1,0 +1,434 @@
+// raster.h -- VS (Default.hlsl:22-45) and the rasteriser behind DrawIndexedInstanced (PBRApp.cpp:1133) on the device:
+// indexed triangle lists in, the 14 planes of a pbr_attributes_soa, the material plane and the depth plane out
+// (pbr_rasterize, include/pbr/pbr_shade.h; DESIGN.md §12 fixes every operation). Included by shade_kernels.hip (its
+// !PBR_BAL_TU part), so it is compiled with that unit's canonical fp32 flags: no contraction, correctly rounded / and
+// sqrt.
+//
+// Four launches, stream-ordered, none waiting on another workgroup:
+//   1. raster_vertex_kernel: one lane per (draw, vertex): VS, the perspective division, the viewport and the snap
+//      to 1/256 pixel into a RasterVertex record.
+//   2. raster_setup_kernel: one lane per triangle: skip tests, the signed area in int64, culling, the bounding box
+//      clipped to the band. A triangle whose clipped box holds at most kSmallPixels pixels is rasterised by its lane;
+//      the others are appended to the large list through one atomic per wave.
+//   3. raster_large_kernel: a workgroup per large triangle (grid-stride over the list) and kLargeSlabs workgroups
+//      across its 64 x 4 pixel blocks; a block every pixel of which some edge function rejects (its maximum over the
+//      block's corners is negative) is skipped. So one triangle over the whole frame is spread over kLargeSlabs
+//      workgroups, and 10^5 sub-pixel triangles never reach this kernel.
+//   4. raster_resolve_kernel: per pixel (the material resolve's 64 x 8 tile, a pixel pair per lane): the visibility
+//      word names the winning triangle; its records are fetched again, the edge functions and barycentrics
+//      recomputed with the operations of the coverage test, the attributes interpolated and stored.
+// Visibility is one 64-bit word per band pixel, (bits(z) << 32) | triangle ordinal, cleared to all ones and lowered
+// by a global 64-bit atomicMin: the smallest key wins whatever the execution order.
+#pragma once
+
+#include "pbr_device_math.h"
+#include "shade_kernels.h"
+
+namespace pbr {
+
+namespace raster {
+
+constexpr int kSmallPixels = 64;   // clipped bounding boxes up to this many pixels: rasterised by the setup lane
+constexpr int kLargeSlabs = 32;    // workgroups across one large triangle's blocks
+constexpr int kLargeGridX = 1024;  // workgroups (x) striding over the large list
+constexpr int kBlockW = 64, kBlockH = 4;
+
+// mul(v, M)[j] for a row vector: the 4-wide dot ((x + y) + z) + w, M row-major.
+__device__ __forceinline__ float mul4(float x, float y, float z, float w, const float* m, int j) {
+    return ((x * m[j] + y * m[4 + j]) + z * m[8 + j]) + w * m[12 + j];
+}
+// mul(v, (float3x3)M)[j].
+__device__ __forceinline__ float mul3(float x, float y, float z, const float* m, int j) {
+    return (x * m[j] + y * m[4 + j]) + z * m[8 + j];
+}
+
+// The draw that holds element g of a prefix-summed range: the largest d with prefix[d] <= g (g < prefix[n]).
+__device__ __forceinline__ int find_draw(const uint32_t* prefix, int n, uint32_t g) {
+    int lo = 0, hi = n;
+    for (int it = 0; it < 32 && hi - lo > 1; ++it) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (prefix[PBR_BOUNDS((int64_t)mid, (int64_t)n + 1, kBoundsRaster)] <= g)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
+enum TriStatus { kTriDraw = 0, kTriNear, kTriGuard, kTriZeroArea, kTriCulled };
+
+// A triangle after setup: its vertices' records and snapped positions in the order every
+// later step uses (1 and 2 exchanged for a back face drawn under cull none), the positive area, the draw.
+struct Tri {
+    uint32_t rec[3];
+    int X[3], Y[3];
+    long long A;
+    int draw;
+};
+
+__device__ __forceinline__ TriStatus tri_setup(const RasterArgs& a, uint32_t t, Tri& s) {
+    const int d = find_draw(a.tri_prefix, a.n_draws, t);
+    s.draw = d;
+    const RasterDraw& dr = a.draws[PBR_BOUNDS((int64_t)d, (int64_t)a.n_draws, kBoundsRaster)];
+    const uint32_t k = t - a.tri_prefix[PBR_BOUNDS((int64_t)d, (int64_t)a.n_draws + 1, kBoundsRaster)];
+    const int64_t i0 = (int64_t)dr.idx_src + 3 * (int64_t)k;
+    uint32_t flags = 0;
+#pragma unroll
+    for (int v = 0; v < 3; ++v) {
+        const uint32_t idx = a.indices[PBR_BOUNDS(i0 + v, a.n_src_indices, kBoundsMesh)];
+        s.rec[v] = dr.rec_base + idx;
+        const RasterVertex& r = a.records[PBR_BOUNDS((int64_t)s.rec[v], (int64_t)a.n_records, kBoundsRaster)];
+        s.X[v] = r.X;
+        s.Y[v] = r.Y;
+        flags |= r.flags;
+    }
+    if (flags & kVertexNear) return kTriNear;
+    if (flags & kVertexGuard) return kTriGuard;
+    long long A = (long long)(s.X[1] - s.X[0]) * (long long)(s.Y[2] - s.Y[0]) -
+                  (long long)(s.X[2] - s.X[0]) * (long long)(s.Y[1] - s.Y[0]);
+    if (A == 0) return kTriZeroArea;
+    if (A < 0) {
+        if (dr.cull == 0u) return kTriCulled;
+        const uint32_t r1 = s.rec[1];
+        s.rec[1] = s.rec[2];
+        s.rec[2] = r1;
+        const int x1 = s.X[1], y1 = s.Y[1];
+        s.X[1] = s.X[2], s.Y[1] = s.Y[2];
+        s.X[2] = x1, s.Y[2] = y1;
+        A = -A;
+    }
+    s.A = A;
+    return kTriDraw;
+}
+
+// The pixels whose centres can lie inside the triangle, clipped to the band; false when there are none.
+struct Box {
+    int x0, x1, y0, y1;  // inclusive
+};
+__device__ __forceinline__ bool tri_box(const RasterArgs& a, const Tri& s, Box& b) {
+    const int minx = min(s.X[0], min(s.X[1], s.X[2])), maxx = max(s.X[0], max(s.X[1], s.X[2]));
+    const int miny = min(s.Y[0], min(s.Y[1], s.Y[2])), maxy = max(s.Y[0], max(s.Y[1], s.Y[2]));
+    // centre 256 p + 128 in [min, max]  <=>  p in [ceil((min - 128) / 256), floor((max - 128) / 256)]
+    b.x0 = max((minx - 128 + 255) >> 8, 0);
+    b.x1 = min((maxx - 128) >> 8, a.width - 1);
+    b.y0 = max((miny - 128 + 255) >> 8, a.row_begin);
+    b.y1 = min((maxy - 128) >> 8, a.row_end - 1);
+    return b.x0 <= b.x1 && b.y0 <= b.y1;
+}
+
+// Edge e of the triangle runs from vertex (e + 1) % 3 to vertex (e + 2) % 3: E0 = 1->2, E1 = 2->0, E2 = 0->1.
+struct Edges {
+    int dx[3], dy[3], xa[3], ya[3];
+    bool top_left[3];
+};
+__device__ __forceinline__ void tri_edges(const Tri& s, Edges& e) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int va = (k + 1) % 3, vb = (k + 2) % 3;
+        e.dx[k] = s.X[vb] - s.X[va];
+        e.dy[k] = s.Y[vb] - s.Y[va];
+        e.xa[k] = s.X[va];
+        e.ya[k] = s.Y[va];
+        e.top_left[k] = e.dy[k] < 0 || (e.dy[k] == 0 && e.dx[k] > 0);
+    }
+}
+// E = (Xb - Xa)(Py - Ya) - (Yb - Ya)(Px - Xa) at the centre of pixel (x, y), exact in int64.
+__device__ __forceinline__ long long edge_at(const Edges& e, int k, int x, int y) {
+    const int px = 256 * x + 128, py = 256 * y + 128;
+    return (long long)e.dx[k] * (long long)(py - e.ya[k]) - (long long)e.dy[k] * (long long)(px - e.xa[k]);
+}
+__device__ __forceinline__ bool covered(const Edges& e, const long long E[3]) {
+    bool in = true;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) in = in && (E[k] > 0 || (E[k] == 0 && e.top_left[k]));
+    return in;
+}
+// l_i = (float)E_i / (float)A: the conversions round to nearest.
+__device__ __forceinline__ void barycentrics(const long long E[3], long long A, float l[3]) {
+    const float fa = (float)A;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) l[k] = (float)E[k] / fa;
+}
+__device__ __forceinline__ float interpolate_z(const float l[3], const float z[3]) {
+    return ((l[0] * z[0] + l[1] * z[1]) + l[2] * z[2]) + 0.0f;
+}
+
+// Coverage, depth range and the visibility update of one pixel (steps 5-7); 1 when a fragment exists.
+__device__ __forceinline__ uint32_t raster_pixel(const RasterArgs& a, const Tri& s, const Edges& e, const float z[3],
+                                                 uint32_t prim, int x, int y) {
+    const long long E[3] = {edge_at(e, 0, x, y), edge_at(e, 1, x, y), edge_at(e, 2, x, y)};
+    if (!covered(e, E)) return 0u;
+    float l[3];
+    barycentrics(E, s.A, l);
+    const float zf = interpolate_z(l, z);
+    if (!(zf >= 0.0f && zf < 1.0f)) return 0u;  // depth clip and LESS against 1; NaN: no fragment
+    const unsigned long long key = ((unsigned long long)__float_as_uint(zf) << 32) | (unsigned long long)prim;
+    [[maybe_unused]] const int64_t n_vis = (int64_t)(a.row_end - a.row_begin) * a.width;
+    atomicMin(a.vis + PBR_BOUNDS((int64_t)(y - a.row_begin) * a.width + x, n_vis, kBoundsRaster), key);
+    return 1u;
+}
+
+__device__ __forceinline__ void load_z(const RasterArgs& a, const Tri& s, float z[3]) {
+#pragma unroll
+    for (int v = 0; v < 3; ++v) z[v] = a.records[PBR_BOUNDS((int64_t)s.rec[v], (int64_t)a.n_records, kBoundsRaster)].z;
+}
+
+// Sum over the wave, then one atomic from its first lane. Every lane of the wave calls it.
+__device__ __forceinline__ void count_wave(unsigned long long* counter, uint32_t mine) {
+    unsigned long long v = mine;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    if ((threadIdx.x & 63u) == 0u && v != 0ull) atomicAdd(counter, v);
+}
+__device__ __forceinline__ void count_ballot(unsigned long long* counter, bool mine) {
+    const uint64_t m = __ballot(mine);
+    if ((threadIdx.x & 63u) == 0u && m != 0ull) atomicAdd(counter, (unsigned long long)__popcll(m));
+}
+
+}  // namespace raster
+
+// Stage 1: VS (Default.hlsl:27-42), the perspective division, the viewport and the snap.
+__global__ __launch_bounds__(256) void raster_vertex_kernel(const RasterArgs a) {
+    using namespace raster;
+    const uint32_t g = blockIdx.x * 256u + threadIdx.x;
+    if (g >= a.n_records) return;
+    const int d = find_draw(a.rec_prefix, a.n_draws, g);
+    const RasterDraw& dr = a.draws[PBR_BOUNDS((int64_t)d, (int64_t)a.n_draws, kBoundsRaster)];
+    const uint32_t v = g - a.rec_prefix[PBR_BOUNDS((int64_t)d, (int64_t)a.n_draws + 1, kBoundsRaster)];
+    const float* in = a.vertices + 14 * PBR_BOUNDS((int64_t)dr.vtx_src + (int64_t)v, a.n_src_vertices, kBoundsMesh);
+    RasterVertex o;
+    float pw[4], ph[4], tc[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) pw[j] = mul4(in[0], in[1], in[2], 1.0f, dr.world, j);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        o.a[j] = pw[j];
+        o.a[3 + j] = mul3(in[3], in[4], in[5], dr.world, j);
+        o.a[6 + j] = mul3(in[6], in[7], in[8], dr.world, j);
+        o.a[9 + j] = mul3(in[9], in[10], in[11], dr.world, j);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ph[j] = mul4(pw[0], pw[1], pw[2], pw[3], a.view_proj, j);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) tc[j] = mul4(in[12], in[13], 0.0f, 1.0f, dr.tex, j);
+    o.a[12] = mul4(tc[0], tc[1], tc[2], tc[3], dr.mat, 0);
+    o.a[13] = mul4(tc[0], tc[1], tc[2], tc[3], dr.mat, 1);
+
+    const float w = ph[3];
+    uint32_t flags = w > 0.0f ? 0u : kVertexNear;  // NaN: near
+    const float nx = ph[0] / w, ny = ph[1] / w, nz = ph[2] / w;
+    const float xs = (nx * 0.5f + 0.5f) * (float)a.width, ys = (0.5f - ny * 0.5f) * (float)a.height;
+    const float tx = xs * 256.0f, ty = ys * 256.0f;
+    const bool inside = fabsf(tx) < 0x1p23f && fabsf(ty) < 0x1p23f;  // false for NaN and inf
+    if (!inside) flags |= kVertexGuard;
+    o.X = inside ? (int)rintf(tx) : 0;
+    o.Y = inside ? (int)rintf(ty) : 0;
+    o.z = nz;
+    o.rw = 1.0f / w;
+    o.flags = flags;
+    o.pad = 0u;
+    a.records[PBR_BOUNDS((int64_t)g, (int64_t)a.n_records, kBoundsRaster)] = o;
+}
+
+// Stage 2: setup of every triangle, the statistics, the small triangles' coverage, the large list.
+__global__ __launch_bounds__(256) void raster_setup_kernel(const RasterArgs a) {
+    using namespace raster;
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    const bool valid = t < a.n_tris;
+    Tri s;
+    TriStatus st = kTriZeroArea;
+    if (valid) st = tri_setup(a, t, s);
+    count_ballot(a.counters + kRasterCulled, valid && st == kTriCulled);
+    count_ballot(a.counters + kRasterZeroArea, valid && st == kTriZeroArea);
+    count_ballot(a.counters + kRasterNear, valid && st == kTriNear);
+    count_ballot(a.counters + kRasterGuard, valid && st == kTriGuard);
+    Box b{0, -1, 0, -1};
+    const bool draw = valid && st == kTriDraw && tri_box(a, s, b);
+    const long long npix = draw ? (long long)(b.x1 - b.x0 + 1) * (long long)(b.y1 - b.y0 + 1) : 0;
+    const bool small = draw && npix <= kSmallPixels, large = draw && !small;
+
+    uint32_t frags = 0;
+    if (small) {
+        Edges e;
+        tri_edges(s, e);
+        float z[3];
+        load_z(a, s, z);
+        for (int y = b.y0; y <= b.y1; ++y)
+            for (int x = b.x0; x <= b.x1; ++x) frags += raster_pixel(a, s, e, z, t, x, y);
+    }
+    count_wave(a.counters + kRasterFragments, frags);
+
+    // one atomic per wave for its large triangles
+    const uint64_t m = __ballot(large);
+    if (m != 0ull) {
+        const uint32_t lane = threadIdx.x & 63u;
+        const int leader = (int)__builtin_ctzll(m);
+        unsigned long long base = 0;
+        if ((int)lane == leader) base = atomicAdd(a.counters + kRasterLarge, (unsigned long long)__popcll(m));
+        base = __shfl(base, leader, 64);
+        if (large) {  // the triangle and its block count: a workgroup whose slab has no block of it skips it unread
+            const uint32_t rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+            const uint32_t nb = ((uint32_t)(b.x1 - b.x0) / kBlockW + 1u) * ((uint32_t)(b.y1 - b.y0) / kBlockH + 1u);
+            a.large[PBR_BOUNDS((int64_t)base + rank, (int64_t)a.n_tris, kBoundsRaster)] = make_uint2(t, nb);
+        }
+    }
+}
+
+// Stage 3: the large triangles. blockIdx.x strides over the list, blockIdx.y over the triangle's 64 x 4 blocks; a wave
+// is one row of a block. All control flow outside the pixel test is uniform over the workgroup.
+__global__ __launch_bounds__(256) void raster_large_kernel(const RasterArgs a) {
+    using namespace raster;
+    const unsigned long long listed = a.counters[kRasterLarge];
+    const uint32_t n_large = listed < (unsigned long long)a.n_tris ? (uint32_t)listed : a.n_tris;
+    uint32_t frags = 0;
+    for (uint32_t i = blockIdx.x; i < n_large; i += gridDim.x) {
+        const uint2 entry = a.large[PBR_BOUNDS((int64_t)i, (int64_t)a.n_tris, kBoundsRaster)];
+        if (blockIdx.y >= entry.y) continue;
+        const uint32_t t = entry.x;
+        Tri s;
+        Box b;
+        if (tri_setup(a, t, s) != kTriDraw || !tri_box(a, s, b)) continue;  // never: the setup kernel listed it
+        const uint32_t nbx = (uint32_t)(b.x1 - b.x0) / kBlockW + 1u, nby = (uint32_t)(b.y1 - b.y0) / kBlockH + 1u;
+        const uint32_t nb = nbx * nby;
+        if (blockIdx.y >= nb) continue;
+        Edges e;
+        tri_edges(s, e);
+        float z[3];
+        load_z(a, s, z);
+        for (uint32_t blk = blockIdx.y; blk < nb; blk += gridDim.y) {
+            const int X0 = b.x0 + (int)(blk % nbx) * kBlockW, Y0 = b.y0 + (int)(blk / nbx) * kBlockH;
+            const int X1 = min(X0 + kBlockW - 1, b.x1), Y1 = min(Y0 + kBlockH - 1, b.y1);
+            bool reject = false;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {  // an edge function is linear: its maximum over the block is at a corner
+                const long long m = max(max(edge_at(e, k, X0, Y0), edge_at(e, k, X1, Y0)),
+                                        max(edge_at(e, k, X0, Y1), edge_at(e, k, X1, Y1)));
+                reject = reject || m < 0;
+            }
+            if (reject) continue;
+            const int x = X0 + (int)(threadIdx.x & 63u), y = Y0 + (int)(threadIdx.x >> 6);
+            if (x <= X1 && y <= Y1) frags += raster_pixel(a, s, e, z, t, x, y);
+        }
+    }
+    count_wave(a.counters + kRasterFragments, frags);
+}
+
+namespace raster {
+
+// One pixel of the band: the winner's attributes (step 8) or the background (step 9).
+__device__ __forceinline__ void resolve_pixel(const RasterArgs& a, int x, int y, float out[14], uint32_t& material,
+                                              float& depth) {
+    [[maybe_unused]] const int64_t n_vis = (int64_t)(a.row_end - a.row_begin) * a.width;
+    const unsigned long long key = a.vis[PBR_BOUNDS((int64_t)(y - a.row_begin) * a.width + x, n_vis, kBoundsRaster)];
+    Tri s;
+    if (key == ~0ull || tri_setup(a, (uint32_t)key, s) != kTriDraw) {  // (a winner always sets up as drawn)
+        const float sx = (float)(2 * x + 1) / (float)a.width - 1.0f;
+        const float sy = 1.0f - (float)(2 * y + 1) / (float)a.height;
+        float d[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) d[c] = (a.fwd[c] + sx * a.right[c]) + sy * a.up[c];
+        const float len = sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float n = d[c] / len;
+            out[3 + c] = n;
+            out[c] = a.eye[c] + n * 100.0f;
+        }
+#pragma unroll
+        for (int k = 6; k < 14; ++k) out[k] = 0.0f;
+        material = 0xFFFFu;
+        depth = 1.0f;
+        return;
+    }
+    Edges e;
+    tri_edges(s, e);
+    const long long E[3] = {edge_at(e, 0, x, y), edge_at(e, 1, x, y), edge_at(e, 2, x, y)};
+    float l[3], p[3], q[3];
+    barycentrics(E, s.A, l);
+    const RasterVertex* r[3];
+#pragma unroll
+    for (int v = 0; v < 3; ++v) r[v] = a.records + PBR_BOUNDS((int64_t)s.rec[v], (int64_t)a.n_records, kBoundsRaster);
+    const float z[3] = {r[0]->z, r[1]->z, r[2]->z};
+    depth = interpolate_z(l, z);  // the key's z: the same operations on the same values
+#pragma unroll
+    for (int v = 0; v < 3; ++v) p[v] = l[v] * r[v]->rw;
+    const float sum = (p[0] + p[1]) + p[2];
+#pragma unroll
+    for (int v = 0; v < 3; ++v) q[v] = p[v] / sum;
+#pragma unroll
+    for (int k = 0; k < 14; ++k) out[k] = (q[0] * r[0]->a[k] + q[1] * r[1]->a[k]) + q[2] * r[2]->a[k];
+    material = a.draws[PBR_BOUNDS((int64_t)s.draw, (int64_t)a.n_draws, kBoundsRaster)].material;
+}
+
+}  // namespace raster
+
+// Stage 4: per pixel, the material resolve's tile: 256 threads over 64 x 8 pixels, a pixel pair per lane, 8-byte
+// plane stores when VEC.
+template <bool VEC>
+__global__ __launch_bounds__(256) void raster_resolve_kernel(const RasterArgs a) {
+    using namespace raster;
+    const int band_h = a.row_end - a.row_begin;
+    const int x = (int)blockIdx.x * 64 + (int)(threadIdx.x & 31u) * 2;
+    const int yb = (int)blockIdx.y * 8 + (int)(threadIdx.x >> 5);  // row of the band
+    const bool in0 = yb < band_h && x < a.width, in1 = yb < band_h && x + 1 < a.width;
+    float v0[14], v1[14], z0 = 1.0f, z1 = 1.0f;
+    uint32_t m0 = 0xFFFFu, m1 = 0xFFFFu;
+    if (in0) resolve_pixel(a, x, a.row_begin + yb, v0, m0, z0);
+    if (in1) resolve_pixel(a, x + 1, a.row_begin + yb, v1, m1, z1);
+    const int64_t oi = (int64_t)yb * a.stride + x;
+    if (VEC && in1) {
+        const int64_t i = PBR_BOUNDS_PIXEL(oi, a.width, band_h, a.stride, 2, kBoundsOutput);
+#pragma unroll
+        for (int k = 0; k < 14; ++k) *reinterpret_cast<float2*>(a.plane[k] + i) = make_float2(v0[k], v1[k]);
+        *reinterpret_cast<uint32_t*>(a.material + i) = m0 | (m1 << 16);
+        if (a.depth) *reinterpret_cast<float2*>(a.depth + i) = make_float2(z0, z1);
+    } else {
+        if (in0) {
+            const int64_t i = PBR_BOUNDS_PIXEL(oi, a.width, band_h, a.stride, 1, kBoundsOutput);
+#pragma unroll
+            for (int k = 0; k < 14; ++k) a.plane[k][i] = v0[k];
+            a.material[i] = (uint16_t)m0;
+            if (a.depth) a.depth[i] = z0;
+        }
+        if (in1) {
+            const int64_t i = PBR_BOUNDS_PIXEL(oi + 1, a.width, band_h, a.stride, 1, kBoundsOutput);
+#pragma unroll
+            for (int k = 0; k < 14; ++k) a.plane[k][i] = v1[k];
+            a.material[i] = (uint16_t)m1;
+            if (a.depth) a.depth[i] = z1;
+        }
+    }
+}
+
+hipError_t launch_raster_vertices(const RasterArgs& a, hipStream_t stream) {
+    if (a.n_records == 0u) return hipSuccess;
+    hipLaunchKernelGGL(raster_vertex_kernel, dim3((a.n_records + 255u) / 256u), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_raster_setup(const RasterArgs& a, hipStream_t stream) {
+    if (a.n_tris == 0u) return hipSuccess;
+    hipLaunchKernelGGL(raster_setup_kernel, dim3((uint32_t)(((uint64_t)a.n_tris + 255u) / 256u)), dim3(256), 0, stream,
+                       a);
+    return hipGetLastError();
+}
+
+hipError_t launch_raster_large(const RasterArgs& a, hipStream_t stream) {
+    if (a.n_tris == 0u) return hipSuccess;
+    const uint32_t gx = a.n_tris < (uint32_t)raster::kLargeGridX ? a.n_tris : (uint32_t)raster::kLargeGridX;
+    hipLaunchKernelGGL(raster_large_kernel, dim3(gx, raster::kLargeSlabs), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_raster_resolve(const RasterArgs& a, hipStream_t stream) {
+    const int band_h = a.row_end - a.row_begin;
+    if (a.width <= 0 || band_h <= 0) return hipSuccess;
+    const dim3 grid((a.width + 63) / 64, (band_h + 7) / 8);
+    if (a.vec)
+        hipLaunchKernelGGL((raster_resolve_kernel<true>), grid, dim3(256), 0, stream, a);
+    else
+        hipLaunchKernelGGL((raster_resolve_kernel<false>), grid, dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
+}  // namespace pbr

@@ -199,6 +199,7 @@ class Attributes:
             raise ValueError("material must be an (H, W) 16-bit integer plane with the planes' row stride and device")
         self.planes = planes
         self.material = material
+        self.depth: Optional[torch.Tensor] = None  # set by ShadingContext.rasterize
         self.height = planes.shape[1]
         self.width = planes.shape[2] if width is None else width
         self.row_stride = planes.stride(1)
@@ -227,6 +228,89 @@ class Attributes:
         a.material = self.material.data_ptr()
         a.width, a.height, a.row_stride = int(self.width), int(self.height), int(self.row_stride)
         return a
+
+
+IDENTITY4 = tuple(np.eye(4, dtype=np.float32).ravel().tolist())
+
+
+def _matrix16(m) -> list:
+    a = np.asarray(m, dtype=np.float32).reshape(-1)
+    if a.size != 16:
+        raise ValueError("a matrix is 16 floats, row-major")
+    return a.tolist()
+
+
+@dataclass
+class Mesh:
+    """One indexed triangle list on the host (pbr_mesh_desc): ``vertices`` (n, 14) float32 in the reference's
+    ``Vertex`` order (FrameResource.h:46-52: Pos, Normal, Tangent, Bitangent, TexCoord), ``indices`` uint32."""
+    vertices: np.ndarray
+    indices: np.ndarray
+
+    def __post_init__(self):
+        self.vertices = np.ascontiguousarray(self.vertices, dtype=np.float32).reshape(-1, 14)
+        self.indices = np.ascontiguousarray(self.indices, dtype=np.uint32).reshape(-1)
+
+
+@dataclass
+class Draw:
+    """One render item (pbr_draw; RenderItem + DrawIndexedInstanced, PBRApp.cpp:1103-1134). Matrices are row-major
+    and multiply a row vector, as ``mul(v, M)`` in Default.hlsl:27-42. ``index_count`` None: to the mesh's end."""
+    mesh: int = 0
+    material: int = 0
+    world: Sequence[float] = IDENTITY4
+    tex_transform: Sequence[float] = IDENTITY4
+    mat_transform: Sequence[float] = IDENTITY4
+    cull: int = 0  # 0 = back faces culled (D3D12_DEFAULT), 1 = none
+    first_index: int = 0
+    index_count: Optional[int] = None
+
+    def to_c(self, meshes: Sequence[Mesh] = ()) -> N.DrawDesc:
+        d = N.DrawDesc()
+        d.mesh, d.first_index, d.material, d.cull = int(self.mesh), int(self.first_index), int(self.material), int(self.cull)
+        if self.index_count is None:
+            if not 0 <= self.mesh < len(meshes):
+                raise ValueError("Draw.index_count is None and the mesh is unknown")
+            d.index_count = int(meshes[self.mesh].indices.size) - int(self.first_index)
+        else:
+            d.index_count = int(self.index_count)
+        d.world[:] = _matrix16(self.world)
+        d.tex_transform[:] = _matrix16(self.tex_transform)
+        d.mat_transform[:] = _matrix16(self.mat_transform)
+        return d
+
+
+@dataclass
+class View:
+    """pbr_raster_view: ``view_proj`` (row-major, row vectors, depth 0..1), the full frame's size, the row band the
+    targets hold, and the background basis: a pixel without a fragment gets
+    ``normalize(bg_forward + sx * bg_right + sy * bg_up)`` as its direction (scenes.look_at_view makes one)."""
+    view_proj: Sequence[float]
+    width: int
+    height: int
+    eye: Sequence[float] = (0.0, 0.0, 0.0)
+    bg_right: Sequence[float] = (1.0, 0.0, 0.0)
+    bg_up: Sequence[float] = (0.0, 1.0, 0.0)
+    bg_forward: Sequence[float] = (0.0, 0.0, 1.0)
+    row_begin: int = 0
+    row_end: Optional[int] = None
+
+    def rows(self, r0: int, r1: int) -> "View":
+        """The same view over rows [r0, r1) of the frame."""
+        from dataclasses import replace
+        return replace(self, row_begin=int(r0), row_end=int(r1))
+
+    def to_c(self) -> N.RasterView:
+        v = N.RasterView()
+        v.view_proj[:] = _matrix16(self.view_proj)
+        v.width, v.height = int(self.width), int(self.height)
+        v.row_begin = int(self.row_begin)
+        v.row_end = int(self.height if self.row_end is None else self.row_end)
+        v.eye[:] = [float(x) for x in self.eye]
+        v.bg_right[:] = [float(x) for x in self.bg_right]
+        v.bg_up[:] = [float(x) for x in self.bg_up]
+        v.bg_forward[:] = [float(x) for x in self.bg_forward]
+        return v
 
 
 def _stream_handle(stream) -> int:
@@ -348,6 +432,61 @@ class ShadingContext:
                 "pbr_resolve_materials", self._h)
         return gb, coverage
 
+    def set_meshes(self, meshes: Sequence[Mesh], stream=None) -> None:
+        """Upload the meshes :meth:`rasterize` draws from (pbr_set_meshes; the vertex / index buffer uploads of
+        BuildShapeGeometry). An index outside its mesh raises ``PbrError(PBR_ERR_INVALID_ARGUMENT)``."""
+        meshes = list(meshes)
+        descs = (N.MeshDesc * max(len(meshes), 1))()
+        for d, m in zip(descs, meshes):
+            d.vertices, d.indices = m.vertices.ctypes.data, m.indices.ctypes.data
+            d.n_vertices, d.n_indices = m.vertices.shape[0], m.indices.size
+        N.check(self.lib.pbr_set_meshes(self._h, descs, len(meshes), ctypes.c_void_p(_stream_handle(stream))),
+                "pbr_set_meshes", self._h)
+        self.meshes = meshes
+
+    def rasterize(self, draws: Sequence[Draw], view: View, out=None, stream=None) -> Attributes:
+        """VS and the rasteriser on the device (pbr_rasterize): ``draws`` in order under ``view`` into
+        the attribute planes :meth:`resolve` consumes, asynchronously. ``out``: an ``Attributes`` holding the view's
+        row band, or an ``(Attributes, depth)`` pair with an (H, row_stride) float32 depth plane; default: fresh
+        tensors. The result carries the depth plane as ``.depth`` (None when ``out`` had none)."""
+        v = view.to_c()
+        rows = v.row_end - v.row_begin
+        dev = torch.device("cuda", self.device)
+        if out is None:
+            attrs = Attributes(torch.empty((N.NUM_ATTRIBUTE_PLANES, max(rows, 0), view.width), dtype=torch.float32, device=dev),
+                               torch.empty((max(rows, 0), view.width), dtype=torch.int16, device=dev))
+            depth = torch.empty((max(rows, 0), view.width), dtype=torch.float32, device=dev)
+        elif isinstance(out, Attributes):
+            attrs, depth = out, None
+        else:
+            attrs, depth = out
+        self._check_device(attrs.planes, attrs.material, depth)
+        if attrs.height < rows or attrs.width < view.width:
+            raise ValueError("out is smaller than the view's band")
+        if depth is not None and (depth.dtype != torch.float32 or depth.dim() != 2 or depth.stride(1) != 1 or
+                                  depth.shape[0] < rows or depth.stride(0) != attrs.row_stride):
+            raise ValueError("depth must be an (H, W) float32 plane with the attribute planes' row stride")
+        t = N.RasterTargets()
+        ps = attrs.planes.stride(0) * 4
+        t.planes[:] = [attrs.planes.data_ptr() + i * ps for i in range(N.NUM_ATTRIBUTE_PLANES)]
+        t.material = attrs.material.data_ptr()
+        t.depth = None if depth is None else depth.data_ptr()
+        t.row_stride = int(attrs.row_stride)
+        meshes = getattr(self, "meshes", ())
+        c_draws = (N.DrawDesc * max(len(draws), 1))(*[d.to_c(meshes) for d in draws])
+        N.check(self.lib.pbr_rasterize(self._h, c_draws, len(draws), ctypes.byref(v), ctypes.byref(t),
+                                       ctypes.c_void_p(_stream_handle(stream))), "pbr_rasterize", self._h)
+        attrs.depth = depth
+        return attrs
+
+    def raster_stats(self, stream=None) -> dict:
+        """pbr_last_raster_stats of the last :meth:`rasterize` on ``stream`` (synchronises it): triangles,
+        backface_culled, zero_area, skipped_near, skipped_guard_band, fragments."""
+        st = N.RasterStats()
+        N.check(self.lib.pbr_last_raster_stats(self._h, ctypes.byref(st), ctypes.c_void_p(_stream_handle(stream))),
+                "pbr_last_raster_stats", self._h)
+        return {name: getattr(st, name) for name, _ in N.RasterStats._fields_}
+
     def _check_device(self, *tensors) -> None:
         """Every tensor handed to the kernel must live on this context's device: a foreign pointer would be
         dereferenced by the kernel (peer access or a fault)."""
@@ -425,7 +564,7 @@ class ShadingContext:
         then clears the flags when ``reset``. Raises PbrError(PBR_ERR_UNSUPPORTED) on a product build."""
         flags = (ctypes.c_uint32 * 16)()
         N.check(self.lib.pbr_debug_bounds(self._h, flags, int(reset)), "pbr_debug_bounds", self._h)
-        names = ("gbuffer", "output", "coverage", "texel", "light", "lds")
+        names = ("gbuffer", "output", "coverage", "texel", "light", "lds", "raster", "mesh")
         return {n: int(flags[8 + c]) for c, n in enumerate(names) if flags[c]}
 
     def cull_stats(self, stream=None):

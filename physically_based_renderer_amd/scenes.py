@@ -22,7 +22,7 @@ import numpy as np
 
 from . import _native as N
 from . import envmap
-from .renderer import Attributes, GBuffer, Material, PassConstants
+from .renderer import Attributes, Draw, GBuffer, Material, Mesh, PassConstants, View
 
 ASSET_DIR = envmap.ASSET_DIR
 
@@ -256,6 +256,91 @@ def build_attributes(cfg: SceneConfig, device, row_begin: int = 0, row_end: Opti
     """Fill rows of attributes on the host and upload them; :meth:`ShadingContext.resolve` makes the G-buffer."""
     planes, mat = fill_attributes_host(cfg, row_begin, row_end, n_threads)
     return Attributes.from_host(planes, mat, device)
+
+
+# ---- Geometry for the device rasteriser (ShadingContext.rasterize; DESIGN.md §12) ------------------------------------
+
+def uv_sphere(slices: int = 64, stacks: int = 32, radius: float = 1.0) -> Mesh:
+    """A UV sphere in the frame the analytic fill uses: theta = atan2(z, x) in [0, 2 pi], phi the
+    angle from +y, P = r (sin phi cos theta, cos phi, sin phi sin theta); N = P / r, UV = (theta / 2 pi, phi / pi),
+    T = dP/dtheta = (-P.z, 0, P.x), B = cross(N, T). (stacks + 1) rings of (slices + 1) vertices (the seam column is
+    doubled so that u runs to 1); the pole quads keep their one triangle with area. Triangles are wound so that the
+    outside is the front face under D3D's default (clockwise seen from outside, left-handed)."""
+    if slices < 3 or stacks < 2:
+        raise ValueError("uv_sphere: at least 3 slices and 2 stacks")
+    j, i = np.meshgrid(np.arange(stacks + 1), np.arange(slices + 1), indexing="ij")
+    theta, phi = 2.0 * np.pi * i / slices, np.pi * j / stacks
+    n = np.stack([np.sin(phi) * np.cos(theta), np.cos(phi), np.sin(phi) * np.sin(theta)], -1)
+    p = radius * n
+    t = np.stack([-p[..., 2], np.zeros_like(phi), p[..., 0]], -1)
+    b = np.cross(n, t)
+    uv = np.stack([i / slices, j / stacks], -1)
+    vertices = np.concatenate([p, n, t, b, uv], -1).reshape(-1, 14).astype(np.float32)
+    ring = slices + 1
+    tris = []
+    for r in range(stacks):
+        for c in range(slices):
+            v00, v01, v10, v11 = r * ring + c, r * ring + c + 1, (r + 1) * ring + c, (r + 1) * ring + c + 1
+            if r != 0:  # the top ring is one point: v00 == v01 in space
+                tris.append((v00, v01, v10))
+            if r != stacks - 1:  # so is the bottom ring
+                tris.append((v01, v11, v10))
+    idx = np.array(tris, np.uint32)
+    # orient: cross(e1, e2) along the outward normal is the front face in a left-handed frame
+    pos = vertices[:, 0:3].astype(np.float64)
+    e1, e2 = pos[idx[:, 1]] - pos[idx[:, 0]], pos[idx[:, 2]] - pos[idx[:, 0]]
+    flip = np.einsum("ij,ij->i", np.cross(e1, e2), pos[idx].sum(1)) < 0
+    idx[flip] = idx[flip][:, [0, 2, 1]]
+    return Mesh(vertices, idx.reshape(-1))
+
+
+def translation(x: float, y: float, z: float) -> tuple:
+    """A row-vector world matrix (the translation in the last row)."""
+    m = np.eye(4, dtype=np.float32)
+    m[3, 0:3] = (x, y, z)
+    return tuple(m.ravel().tolist())
+
+
+def look_at_view(eye, target, fov_y: float, width: int, height: int, near: float = 0.1, far: float = 100.0) -> View:
+    """The :class:`View` of a left-handed look-at camera with world up (0, 1, 0) and a D3D perspective projection
+    (depth 0 at ``near``, 1 at ``far``; BuildCamera's 0.1 and 100, PBRApp.cpp:654), row vectors: ``view_proj`` =
+    view x projection, and the background basis of the same camera as pbr_attributes_fill builds it."""
+    eye, target = np.asarray(eye, np.float64), np.asarray(target, np.float64)
+    f = (target - eye) / np.linalg.norm(target - eye)
+    r = np.array([f[2], 0.0, -f[0]])  # cross(up, forward)
+    r /= np.linalg.norm(r)
+    u = np.cross(f, r)
+    t, aspect = np.tan(0.5 * fov_y), width / height
+    view = np.eye(4)
+    view[0:3, 0], view[0:3, 1], view[0:3, 2] = r, u, f
+    view[3, 0:3] = (-r @ eye, -u @ eye, -f @ eye)
+    proj = np.zeros((4, 4))
+    proj[0, 0], proj[1, 1] = 1.0 / (aspect * t), 1.0 / t
+    proj[2, 2], proj[2, 3], proj[3, 2] = far / (far - near), 1.0, -near * far / (far - near)
+    vp = (view @ proj).astype(np.float32)
+    return View(view_proj=tuple(vp.ravel().tolist()), width=int(width), height=int(height),
+                eye=tuple(eye.astype(np.float32).tolist()), bg_right=tuple((r * t * aspect).astype(np.float32).tolist()),
+                bg_up=tuple((u * t).astype(np.float32).tolist()), bg_forward=tuple(f.astype(np.float32).tolist()))
+
+
+def reference_sphere_centres() -> list:
+    """(x, y) of the reference scene's 58 unit spheres on z = 0, in material order (scene_materials): the 7 x 7 red
+    grid (PBRApp.cpp:964-973, 1016-1022), then rust, copper and the seven tiles on y = 0 (PBRApp.cpp:1023-1068)."""
+    grid = [((i % 7) * 2.5 - 7.5, -(i // 7) * 2.5 - 2.5) for i in range(49)]
+    return grid + [(x, 0.0) for x in (0.0, -2.5, -5.0, -7.5, -10.0, 2.5, 5.0, 7.5, 10.0)]
+
+
+def reference_scene_draws(slices: int = 64, stacks: int = 32):
+    """(meshes, draws) of the reference scene for :meth:`ShadingContext.rasterize`: one UV sphere, 58 draws, draw i
+    with material i. The facets are not the analytic spheres of pbr_attributes_fill."""
+    draws = [Draw(mesh=0, material=i, world=translation(x, y, 0.0)) for i, (x, y) in enumerate(reference_sphere_centres())]
+    return [uv_sphere(slices, stacks)], draws
+
+
+def reference_scene_view(cfg: SceneConfig) -> View:
+    """The :class:`View` of a reference-scene config's camera (None = BuildCamera's default)."""
+    eye, target, fov = cfg.camera or ((0.0, 0.0, -5.0), (0.0, 0.0, 0.0), float(np.pi / 4))
+    return look_at_view(eye, target, fov, cfg.width, cfg.height)
 
 
 def env_map() -> np.ndarray:

@@ -1,0 +1,171 @@
+"""Time the device rasteriser (pbr_rasterize) at 3840x2160 on two scenes, in one process on one GPU:
+
+  reference  the reference's 58 spheres as 64 x 32 UV spheres (3,968 triangles each, 230,144 in all) from the
+             overview camera;
+  stress     ~10^6 triangles of about a pixel, uniformly over the frame.
+
+Four legs per scene:
+  (a) the stages of one call, HIP events between them (pbr_debug_rasterize_timed): clears and table upload, the
+      vertex transform, the setup kernel (with the small triangles' coverage), the large triangles' coverage, the
+      per-pixel resolve; median of --steps calls after a clock ramp;
+  (b) the whole call, events around ShadingContext.rasterize;
+  (c) a device-to-device copy of the bytes the resolve stage writes (14 planes + the id: 58 B per pixel): the
+      streaming yardstick;
+  (d) reference scene only: the host route to the same planes, pbr_attributes_fill on 16 threads plus the upload
+      (the analytic spheres, not the facets: DESIGN.md §12).
+
+    python tools/raster_bench.py [--width 3840 --height 2160] [--steps 50] [--log profiles/r10/raster_bench.log]
+"""
+import argparse
+import ctypes
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from physically_based_renderer_amd import _native as N  # noqa: E402
+from physically_based_renderer_amd import scenes as S  # noqa: E402
+from physically_based_renderer_amd.renderer import Attributes, Draw, Mesh, ShadingContext, View  # noqa: E402
+
+STAGES = ("clear_upload", "vertex", "setup_small", "large", "resolve")
+BYTES_WRITTEN = 14 * 4 + 2
+
+
+def event_ms(fn, steps, ramp_s=0.2):
+    """Median / min / max of `steps` event-bracketed calls after a clock ramp of back-to-back calls."""
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < ramp_s:
+        for _ in range(4):
+            fn()
+        torch.cuda.synchronize()
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
+    for e0, e1 in ev:
+        e0.record()
+        fn()
+        e1.record()
+    torch.cuda.synchronize()
+    ms = sorted(e0.elapsed_time(e1) for e0, e1 in ev)
+    return {"median_ms": ms[len(ms) // 2], "min_ms": ms[0], "max_ms": ms[-1]}
+
+
+def stress_scene(W, H, n_tris, seed=7):
+    """n_tris triangles with vertices within ~0.9 pixel of a random centre, w in [0.5, 2], no culling."""
+    rng = np.random.default_rng(seed)
+    c = rng.uniform((0, 0), (W, H), (n_tris, 1, 2))
+    p = c + rng.uniform(-0.9, 0.9, (n_tris, 3, 2))
+    w = rng.uniform(0.5, 2.0, (n_tris, 3))
+    v = np.zeros((n_tris, 3, 14), np.float32)
+    v[..., 0] = (p[..., 0] / W * 2.0 - 1.0) * w
+    v[..., 1] = (1.0 - p[..., 1] / H * 2.0) * w
+    v[..., 2] = w
+    v[..., 3:] = rng.normal(size=(n_tris, 3, 11)).astype(np.float32)
+    near, far = 0.1, 100.0
+    vp = np.array([[1, 0, 0, 0], [0, 1, 0, 0], [0, 0, far / (far - near), 1], [0, 0, -near * far / (far - near), 0]],
+                  np.float32)
+    view = View(view_proj=tuple(vp.ravel().tolist()), width=W, height=H)
+    return [Mesh(v.reshape(-1, 14), np.arange(3 * n_tris, dtype=np.uint32))], [Draw(cull=1)], view
+
+
+def timed_stages(ctx, draws, view, attrs, depth, steps):
+    """Per-stage medians of `steps` timed calls (each synchronises; the clock ramp is the untimed loop before)."""
+    fn = ctx.lib.pbr_debug_rasterize_timed
+    fn.restype = ctypes.c_int
+    fn.argtypes = [ctypes.c_void_p, ctypes.POINTER(N.DrawDesc), ctypes.c_int32, ctypes.POINTER(N.RasterView),
+                   ctypes.POINTER(N.RasterTargets), ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
+    v = view.to_c()
+    t = N.RasterTargets()
+    ps = attrs.planes.stride(0) * 4
+    t.planes[:] = [attrs.planes.data_ptr() + i * ps for i in range(14)]
+    t.material, t.depth, t.row_stride = attrs.material.data_ptr(), depth.data_ptr(), int(attrs.row_stride)
+    c_draws = (N.DrawDesc * len(draws))(*[d.to_c(ctx.meshes) for d in draws])
+    stream = ctypes.c_void_p(int(torch.cuda.current_stream().cuda_stream))
+    ms = (ctypes.c_float * 5)()
+    rows = []
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < 0.2:  # clock ramp
+        ctx.rasterize(draws, view, out=(attrs, depth))
+    for _ in range(steps):
+        N.check(fn(ctx.handle, c_draws, len(draws), ctypes.byref(v), ctypes.byref(t), stream, ms),
+                "pbr_debug_rasterize_timed", ctx.handle)
+        rows.append(list(ms))
+    med = np.median(np.array(rows), axis=0)
+    return {k: float(x) for k, x in zip(STAGES, med)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--width", type=int, default=3840)
+    ap.add_argument("--height", type=int, default=2160)
+    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--stress-triangles", type=int, default=1_000_000)
+    ap.add_argument("--slices", type=int, default=64)
+    ap.add_argument("--stacks", type=int, default=32)
+    ap.add_argument("--log", default=None, help="append the result lines to this file too")
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("raster_bench: no GPU visible (timings are taken on the device only)")
+    problems = N.build_problems()
+    if problems:
+        sys.exit("raster_bench: not the product build of this checkout: " + "; ".join(problems))
+    W, H = a.width, a.height
+    dev = torch.device("cuda", 0)
+    lines = []
+
+    def emit(d):
+        line = json.dumps(d)
+        print(line, flush=True)
+        lines.append(line)
+
+    emit({"tool": "raster_bench", "width": W, "height": H, "sources_sha": N.build_info()["sources_sha"],
+          "device": torch.cuda.get_device_name(0), "steps": a.steps, "resolve_bytes_per_pixel": BYTES_WRITTEN})
+    cfg = S.REFERENCE_SCENE.with_size(W, H).with_camera(*S.OVERVIEW_CAMERA)
+    ref_meshes, ref_draws = S.reference_scene_draws(a.slices, a.stacks)
+    scenes = [("reference", ref_meshes, ref_draws, S.reference_scene_view(cfg)),
+              ("stress",) + stress_scene(W, H, a.stress_triangles)]
+    attrs = Attributes(torch.empty((14, H, W), dtype=torch.float32, device=dev),
+                       torch.empty((H, W), dtype=torch.int16, device=dev))
+    depth = torch.empty((H, W), dtype=torch.float32, device=dev)
+    src = torch.empty(W * H * BYTES_WRITTEN, dtype=torch.uint8, device=dev)
+    dst = torch.empty_like(src)
+    with ShadingContext(0) as ctx:
+        c = event_ms(lambda: dst.copy_(src), a.steps)
+        c.update(leg="c_d2d_copy_58B_per_pixel", gb_per_s=2 * src.numel() / (c["median_ms"] * 1e-3) / 1e9)
+        emit(c)
+        for name, meshes, draws, view in scenes:
+            ctx.set_meshes(meshes)
+            ctx.rasterize(draws, view, out=(attrs, depth))
+            stats = ctx.raster_stats()
+            covered = int((attrs.material != -1).sum().item())
+            emit({"scene": name, "stats": stats, "covered_pixels": covered,
+                  "vertices": int(sum(m.vertices.shape[0] for m in meshes)), "draws": len(draws)})
+            st = timed_stages(ctx, draws, view, attrs, depth, a.steps)
+            st.update(leg="a_stages_ms", scene=name, coverage_ms=st["setup_small"] + st["large"],
+                      resolve_over_copy=st["resolve"] / c["median_ms"])
+            emit(st)
+            whole = event_ms(lambda: ctx.rasterize(draws, view, out=(attrs, depth)), a.steps)
+            whole.update(leg="b_whole_call", scene=name)
+            emit(whole)
+        host = []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            planes, mat = S.fill_attributes_host(cfg, n_threads=16)
+            t1 = time.perf_counter()
+            Attributes.from_host(planes, mat, dev)
+            torch.cuda.synchronize()
+            host.append((time.perf_counter() - t0, t1 - t0))
+        host.sort()
+        emit({"leg": "d_host_attributes_fill_plus_upload", "scene": "reference (analytic spheres)",
+              "median_ms": host[1][0] * 1e3, "fill_ms": host[1][1] * 1e3})
+    if a.log:
+        os.makedirs(os.path.dirname(os.path.abspath(a.log)), exist_ok=True)
+        with open(a.log, "a") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
