@@ -1,7 +1,7 @@
 // material_resolve.h -- the first half of PS on the device (Default.hlsl:50-116): interpolated VertexOut planes and
 // the material textures in, the 15 planes of a pbr_gbuffer_soa (plus opacity and coverage) out
-// (pbr_resolve_materials, include/pbr/pbr_shade.h). Included by shade_kernels.hip (its !PBR_BAL_TU
-// part), so it is compiled with that unit's canonical fp32 flags: no contraction, correctly rounded / and sqrt.
+// (pbr_resolve_materials, include/pbr/pbr_shade.h). A source of frontend_kernels.hip, which is
+// compiled with the canonical fp32 flags: no contraction, correctly rounded / and sqrt.
 //
 // Layout: a workgroup is 256 threads over a 64 x 8 pixel tile, a lane owns two horizontally adjacent pixels and a
 // wave64 covers 64 x 2 pixels (the shading kernels' tile and culling unit), so with 8-byte aligned planes and even
@@ -20,7 +20,7 @@
 #pragma once
 
 #include "pbr_device_math.h"
-#include "shade_kernels.h"
+#include "frontend_kernels.h"
 
 namespace pbr {
 

@@ -1,18 +1,12 @@
 // pbr_context.hip -- the C ABI of include/pbr/pbr_shade.h: context lifetime, pass/env upload and
-// the shade entry point. Host code only; the kernels live in shade_kernels.hip.
-#include <hip/hip_runtime.h>
-
+// the shade entry point (the front end's entry points are in pbr_frontend.hip). Host code only; the kernels live in
+// shade_kernels.hip.
 #include <cmath>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
-#include <vector>
 #include <new>
-#include <string>
 
-#include "pbr/pbr_shade.h"
-#include "shade_kernels.h"
+#include "pbr_context_impl.h"
 #include "pbr_debug_bounds.h"
 #include "pbr_build_info.h"
 
@@ -21,6 +15,8 @@
 extern "C" {
 extern const char pbr_unit_info_shade_kernels[] __attribute__((weak));
 extern const char pbr_unit_info_shade_kernels_bal[] __attribute__((weak));
+extern const char pbr_unit_info_frontend_kernels[] __attribute__((weak));
+extern const char pbr_unit_info_pbr_frontend[] __attribute__((weak));
 extern const char pbr_unit_info_gbuffer_fill[] __attribute__((weak));
 __attribute__((used)) const char pbr_unit_info_pbr_context[] =
     PBR_UNIT_INFO("pbr_context", PBR_BI_SWITCH(PBR_DEBUG_BOUNDS));
@@ -99,35 +95,7 @@ inline bool zero_or_within(float x, float lo, float hi) {
 // A context used from one stream records nothing per launch (every reader is the writer's stream). The first
 // launch on a second stream synchronises the device once, so the earlier single-stream passes are complete and
 // need no event; from then on each launch records its stream's last_pass.
-struct StreamState {
-    hipStream_t stream = nullptr;
-    hipEvent_t last_pass = nullptr;  // multi-stream contexts: recorded after every launch on `stream`
-    // Statistics of the last pass on this stream: one record of pbr::kStatsPerBlock int32 per statistics slot
-    // (one per wave in the pair layout, per workgroup in the one-pixel layout; pbr::StatField), summed on the
-    // host by pbr_last_pass_stats / pbr_last_cull_stats. Written only by this stream's passes, so a pass never
-    // overwrites the record of a pass on another stream.
-    int32_t* d_stats = nullptr;
-    int64_t stats_capacity = 0;  // slots
-    int64_t tiles = 0, slots = 0;
-    bool culled = false;
-    std::string kernel;  // the last pass's kernel (pbr_last_pass_kernel)
-    // pbr_rasterize on this stream (raster.h): its device scratch -- counters, the draw table, the transformed vertex
-    // records, the large-triangle list, the visibility words -- grown in stream order on this stream, and the pinned
-    // staging of the draw table with the event of its last upload. A stream has its own, so rasterisations queued on
-    // two streams never share scratch.
-    struct Raster {
-        char* d = nullptr;
-        size_t capacity = 0;
-        char* h = nullptr;  // pinned
-        size_t h_capacity = 0;
-        hipEvent_t staged = nullptr;
-        bool staged_pending = false;
-        unsigned long long* d_counters = nullptr;  // inside d
-        int64_t triangles = 0;
-        bool ran = false;
-    };
-    Raster raster;
-};
+// (StreamState, Resource and the context itself: pbr_context_impl.h.)
 
 // After the stream's work is complete (a device synchronisation): give back what a StreamState owns.
 static void release_stream_state(StreamState& st) {
@@ -139,119 +107,23 @@ static void release_stream_state(StreamState& st) {
     st = StreamState{};
 }
 
-struct Resource {
-    std::vector<int> readers;  // StreamState indices that launched a pass reading it since the last write
-    int writer = -1;           // StreamState index of the stream that wrote it last (-1: none / host-complete)
-    hipEvent_t written = nullptr;  // recorded on the writer's stream after the write
-};
-
-struct pbr_context {
-    int device = 0;
-    std::vector<StreamState> streams;
-    // Lights: a ring of device slots (3 float4 per light), each fed from its own pinned staging copy so a host
-    // pass struct can be reused as soon as pbr_set_pass returns. Every pbr_set_pass takes the next slot; a
-    // launch reads the slot of the pass it was queued with, so setting frame k+1's pass (on any stream) never
-    // overwrites the lights a queued frame k reads.
-    static constexpr int kSlots = 4;
-    struct LightSlot {
-        float4* d = nullptr;
-        int capacity = 0;
-        pbr_light* h = nullptr;        // pinned staging, PBR_MAX_LIGHTS records
-        hipEvent_t copied = nullptr;   // the staging -> device copy
-        bool copy_pending = false;
-        Resource use;
-    };
-    LightSlot slots[kSlots];
-    int cur_slot = -1;
-    int next_slot = 0;
-    // Textures: the environment (IBL, g_SkyArray[1]) and the sky (g_SkyArray[0]), each kept as fp32
-    // RGBA on the device (decoded once from R16G16B16A16_UNORM, or uploaded as fp32).
-    struct Texture {
-        uint16_t* d_u16 = nullptr;  // UNORM16 upload staging
-        float4* d = nullptr;
-        int w = 0, h = 0, capacity = 0;
-        bool faithful_ok = true;  // every texel in [0, kFaithfulAmbientHi], none NaN (PBR_FLAG_FAITHFUL precondition for the IBL)
-        Resource use;
-    };
-    Texture env, sky;
-    // The material table and its textures (pbr_set_materials; read by pbr_resolve_materials): the records and one
-    // RGBA8 texel buffer holding every texture, replaced as a whole.
-    struct Materials {
-        pbr::MaterialRec* d_table = nullptr;
-        uint32_t* d_texels = nullptr;
-        int n = 0;
-        int64_t n_texels = 0;
-        bool set = false;
-        Resource use;
-    };
-    Materials mats;
-    // The meshes pbr_rasterize draws from (pbr_set_meshes): every mesh's vertices in one buffer, every index in
-    // another, replaced as a whole; the placement of each mesh stays on the host.
-    struct MeshPlace {
-        uint32_t vtx_base, n_vertices, idx_base, n_indices;
-    };
-    struct Meshes {
-        float* d_vertices = nullptr;
-        uint32_t* d_indices = nullptr;
-        int64_t n_vertices = 0, n_indices = 0;
-        std::vector<MeshPlace> place;
-        bool set = false;
-        Resource use;
-    };
-    Meshes meshes;
-    // Current pass.
-    pbr::PassArgs pass{};
-    int ambient_mode = 0;
-    uint32_t flags = 0;
-    bool pass_set = false;
-    bool faithful_pass_ok = false;  // light strengths and the constant ambient inside PBR_FLAG_FAITHFUL's windows (pbr_set_pass)
-    bool faithful_count_terms = false;  // > 64 lights (culled pass): the kernel counts summed terms per wave
-    int last_stream = -1;  // StreamState index of the context's last pass (pbr_last_pass_stats fallback)
-    // Wave-balanced point-light lists (pbr_balanced.h) for untiled passes with at least this many point lights
-    // and no spot lights; -1: the measured crossover of the mode (kBalancedMinFaithful / kBalancedMinExact);
-    // PBR_BALANCED_MIN overrides both (0 disables).
-    int balanced_min = -1;
-    bool points_flag_ok = false;  // pbr_set_pass: every point light inside the fast-path window
-    bool points_quarter_ok = false;  // ... and every point strength inside the quarter gate (the exact balanced items' 4x radiance)
-    int pixels_per_thread = 2;  // kernel layout: packed pixel pairs (measured faster); PBR_PIXELS_PER_THREAD=1 overrides
-    bool lean = true;  // uniform-loop passes without a sky pass use the lean pair kernel (PBR_LEAN=0: off)
-    std::string last_error;
-    std::mutex mu;
-};
-
-namespace {
-
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = false;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        ok = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
-int fail_hip(pbr_context* ctx, hipError_t e, const char* what, int status = PBR_ERR_HIP) {
+int fail_hip(pbr_context* ctx, hipError_t e, const char* what, int status) {
     if (ctx) {
         ctx->last_error = std::string(what) + ": " + hipGetErrorName(e) + " (" + hipGetErrorString(e) + ")";
     }
     return e == hipErrorOutOfMemory ? PBR_ERR_OUT_OF_MEMORY : status;
 }
 
-bool is_ambient_mode(int m) { return m == PBR_AMBIENT_CONSTANT || m == PBR_AMBIENT_IBL_DIFFUSE; }
-
-void forget_readers(pbr_context* ctx);
+static bool is_ambient_mode(int m) { return m == PBR_AMBIENT_CONSTANT || m == PBR_AMBIENT_IBL_DIFFUSE; }
 
 // PBR_DEBUG_BOUNDS builds (pbr_debug_bounds.h): one bounds-flag buffer per device, allocated, cleared and published
 // to the kernels by the first context created on it; product builds have none.
 constexpr int kBoundsMaxDevices = 64;
 constexpr size_t kBoundsBytes = sizeof(uint32_t) * 2 * pbr::kBoundsClasses;
-std::mutex g_bounds_mu;
-uint32_t* g_bounds_buf[kBoundsMaxDevices] = {};
+static std::mutex g_bounds_mu;
+static uint32_t* g_bounds_buf[kBoundsMaxDevices] = {};
 
-hipError_t arm_bounds(int dev) {  // current device = dev
+static hipError_t arm_bounds(int dev) {  // current device = dev
     if (!PBR_DEBUG_BOUNDS) return hipSuccess;
     if (dev < 0 || dev >= kBoundsMaxDevices) return hipErrorInvalidDevice;
     std::lock_guard<std::mutex> lk(g_bounds_mu);
@@ -260,6 +132,7 @@ hipError_t arm_bounds(int dev) {  // current device = dev
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&b), kBoundsBytes);
     if (e == hipSuccess) e = hipMemset(b, 0, kBoundsBytes);
     if (e == hipSuccess) e = pbr::debug_bounds_publish(b);
+    if (e == hipSuccess) e = pbr::debug_bounds_publish_frontend(b);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e == hipSuccess)
         g_bounds_buf[dev] = b;
@@ -268,14 +141,25 @@ hipError_t arm_bounds(int dev) {  // current device = dev
     return e;
 }
 
-// PBR_DEBUG_BOUNDS_SKEW=1 (bounds-checked builds): the output extent the checks use is one column narrower than
-// the frame, so every pass must report class 1 -- the negative control of tests/test_gpu_debug_bounds.py.
+// PBR_DEBUG_BOUNDS_SKEW=1 (bounds-checked builds): the extents the checks use are too small -- the output extent of a
+// pass one column narrower than the frame, the texel count of a resolve and the index count of a rasterisation 0 -- so
+// every pass must report class "output", every textured resolve "texel" and every rasterisation "mesh": the negative
+// controls of tests/test_gpu_debug_bounds.py. Only the checks read those extents; a flagged index is replaced by 0,
+// which every one of those buffers holds.
 bool debug_bounds_skew() {
     static const bool skew = [] {
         const char* e = std::getenv("PBR_DEBUG_BOUNDS_SKEW");
         return PBR_DEBUG_BOUNDS && e != nullptr && std::atoi(e) != 0;
     }();
     return skew;
+}
+
+// After a device synchronisation: every queued read and write of the context's resources is complete.
+static void forget_readers(pbr_context* ctx) {
+    for (Resource* r : ctx->resources) {
+        r->readers.clear();
+        r->writer = -1;
+    }
 }
 
 // Streams a context tracks at once. Contexts expect a small, long-lived set of streams (a FrameResource-style
@@ -367,23 +251,15 @@ hipError_t before_read(Resource& r, hipStream_t s, int si) {
     return hipSuccess;
 }
 
-// After a device synchronisation: every queued read and write of the context's resources is complete.
-void forget_readers(pbr_context* ctx) {
-    for (pbr_context::LightSlot& sl : ctx->slots) {
-        sl.use.readers.clear();
-        sl.use.writer = -1;
+// A launch on stream `s` (index si) has been queued: record the stream's last_pass, which orders a later write of
+// what the launch read after it, once the context tracks more than one stream.
+int after_launch(pbr_context* ctx, int si, hipStream_t s, const char* what) {
+    if (ctx->streams.size() > 1) {
+        const hipError_t e = hipEventRecord(ctx->streams[si].last_pass, s);
+        if (e != hipSuccess) return fail_hip(ctx, e, what);
     }
-    for (pbr_context::Texture* t : {&ctx->env, &ctx->sky}) {
-        t->use.readers.clear();
-        t->use.writer = -1;
-    }
-    ctx->mats.use.readers.clear();
-    ctx->mats.use.writer = -1;
-    ctx->meshes.use.readers.clear();
-    ctx->meshes.use.writer = -1;
+    return PBR_OK;
 }
-
-}  // namespace
 
 extern "C" {
 
@@ -393,7 +269,8 @@ const char* pbr_build_info(void) {
     static const std::string info = [] {
         std::string r = "{\"abi\": " + std::to_string(PBR_ABI_VERSION) + ", \"units\": [";
         bool first = true;
-        for (const char* u : {pbr_unit_info_pbr_context, pbr_unit_info_shade_kernels, pbr_unit_info_shade_kernels_bal,
+        for (const char* u : {pbr_unit_info_pbr_context, pbr_unit_info_pbr_frontend, pbr_unit_info_shade_kernels,
+                              pbr_unit_info_shade_kernels_bal, pbr_unit_info_frontend_kernels,
                               pbr_unit_info_gbuffer_fill}) {
             if (u == nullptr) continue;
             r += first ? "" : ", ";
@@ -457,25 +334,17 @@ int pbr_context_destroy(pbr_context* ctx) {
     {
         DeviceGuard g(ctx->device);
         (void)hipDeviceSynchronize();
-        // Light slots and textures come from the stream-ordered pool (hipMallocAsync): returned the same way, after
+        // The resources' buffers come from the stream-ordered pool (hipMallocAsync): returned the same way, after
         // the synchronisation above, and the pool's frees completed by the one below.
-        for (pbr_context::LightSlot& sl : ctx->slots) {
+        for (Resource* r : ctx->resources) {
+            for (void** m : r->mem)
+                if (m && *m) (void)hipFreeAsync(*m, nullptr);
+            if (r->written) (void)hipEventDestroy(r->written);
+        }
+        for (pbr_context::LightSlot& sl : ctx->slots) {  // the ring's host side
             if (sl.copied) (void)hipEventDestroy(sl.copied);
             if (sl.h) (void)hipHostFree(sl.h);
-            if (sl.d) (void)hipFreeAsync(sl.d, nullptr);
-            if (sl.use.written) (void)hipEventDestroy(sl.use.written);
         }
-        for (pbr_context::Texture* t : {&ctx->env, &ctx->sky}) {
-            if (t->d_u16) (void)hipFreeAsync(t->d_u16, nullptr);
-            if (t->d) (void)hipFreeAsync(t->d, nullptr);
-            if (t->use.written) (void)hipEventDestroy(t->use.written);
-        }
-        if (ctx->mats.d_table) (void)hipFreeAsync(ctx->mats.d_table, nullptr);
-        if (ctx->mats.d_texels) (void)hipFreeAsync(ctx->mats.d_texels, nullptr);
-        if (ctx->mats.use.written) (void)hipEventDestroy(ctx->mats.use.written);
-        if (ctx->meshes.d_vertices) (void)hipFreeAsync(ctx->meshes.d_vertices, nullptr);
-        if (ctx->meshes.d_indices) (void)hipFreeAsync(ctx->meshes.d_indices, nullptr);
-        if (ctx->meshes.use.written) (void)hipEventDestroy(ctx->meshes.use.written);
         for (StreamState& st : ctx->streams) release_stream_state(st);
         (void)hipDeviceSynchronize();
     }
@@ -496,13 +365,11 @@ int pbr_set_pass(pbr_context* ctx, const pbr_pass_desc* pass, void* stream) {
         PBR_FLAG_ALPHA_TEST;
     if (pass->flags & ~known) return PBR_ERR_INVALID_ARGUMENT;
 
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard g(ctx->device);
-    if (!g.ok) return PBR_ERR_NO_DEVICE;
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    Entry en(ctx);
+    if (const int rc = en.open(stream, "pbr_set_pass stream")) return rc;
+    const hipStream_t s = en.s;
+    const int si = en.si;
     hipError_t e = hipSuccess;
-    const int si = stream_index(ctx, s, e);
-    if (si < 0) return fail_hip(ctx, e, "pbr_set_pass stream");
     // The next slot of the ring: its staging copy must have left the host buffer, and its device copy is
     // overwritten only after the queued passes that read it (stream-side waits, before_write).
     const int slot = ctx->next_slot;
@@ -615,42 +482,23 @@ int set_texture(pbr_context* ctx, pbr_context::Texture& t, const void* texels, b
                 int32_t height, void* stream, const char* what) {
     if (!ctx || !texels || width <= 0 || height <= 0) return PBR_ERR_INVALID_ARGUMENT;
     if ((long long)width * height > (1ll << 26)) return PBR_ERR_INVALID_ARGUMENT;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard g(ctx->device);
-    if (!g.ok) return PBR_ERR_NO_DEVICE;
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    Entry en(ctx);
+    if (const int rc = en.open(stream, what)) return rc;
     const int n = width * height;
-    hipError_t e = hipSuccess;
-    const int si = stream_index(ctx, s, e);
-    if (si < 0) return fail_hip(ctx, e, what);
-    if (n > t.capacity) {
-        // Growing: the old texture may still be read by queued passes (released after them, in stream order).
-        e = free_after_readers(ctx, t.use, t.d_u16, s, si);
-        if (e == hipSuccess && t.d) e = hipFreeAsync(t.d, s);
+    const size_t bytes_u16 = sizeof(uint16_t) * 4 * (size_t)n, bytes_f32 = sizeof(float4) * (size_t)n;
+    // Growing: the old texture may still be read by queued passes (released after them, in stream order); otherwise
+    // it is replaced in place.
+    const bool grow = n > t.capacity;
+    if (grow) t.capacity = 0;
+    const int rc = replace_buffers(en, t.use, grow, bytes_u16, bytes_f32, what, [&] {
+        hipError_t e = unorm16 ? hipMemcpyAsync(t.d_u16, texels, bytes_u16, hipMemcpyHostToDevice, en.s)
+                               : hipMemcpyAsync(t.d, texels, bytes_f32, hipMemcpyHostToDevice, en.s);
         if (e != hipSuccess) return fail_hip(ctx, e, what);
-        t.d_u16 = nullptr;
-        t.d = nullptr;
-        t.capacity = 0;
-        e = hipMallocAsync(reinterpret_cast<void**>(&t.d_u16), sizeof(uint16_t) * 4 * (size_t)n, s);
-        if (e == hipSuccess) e = hipMallocAsync(reinterpret_cast<void**>(&t.d), sizeof(float4) * (size_t)n, s);
-        if (e != hipSuccess) return fail_hip(ctx, e, what);
-        t.capacity = n;
-    }
-    // Replaced in place: after the queued passes (of any stream) that read the old texels.
-    e = before_write(ctx, t.use, s, si);
-    if (e != hipSuccess) return fail_hip(ctx, e, what);
-    if (unorm16) {
-        e = hipMemcpyAsync(t.d_u16, texels, sizeof(uint16_t) * 4 * (size_t)n, hipMemcpyHostToDevice, s);
-        if (e != hipSuccess) return fail_hip(ctx, e, what);
-        e = pbr::launch_decode_unorm16(t.d_u16, t.d, n, s);
-        if (e != hipSuccess) return fail_hip(ctx, e, "decode_unorm16_kernel", PBR_ERR_LAUNCH);
-    } else {
-        e = hipMemcpyAsync(t.d, texels, sizeof(float4) * (size_t)n, hipMemcpyHostToDevice, s);
-        if (e != hipSuccess) return fail_hip(ctx, e, what);
-    }
-    e = hipStreamSynchronize(s);  // the (pageable) host texels may be released on return
-    if (e != hipSuccess) return fail_hip(ctx, e, what);
-    t.use.writer = -1;  // complete: later passes on any stream see the new texels
+        if (unorm16) e = pbr::launch_decode_unorm16(t.d_u16, t.d, n, en.s);
+        return e == hipSuccess ? PBR_OK : fail_hip(ctx, e, "decode_unorm16_kernel", PBR_ERR_LAUNCH);
+    });
+    if (rc != PBR_OK) return rc;
+    if (grow) t.capacity = n;
     t.w = width;
     t.h = height;
     t.faithful_ok = true;  // UNORM16 texels are in [0, 1]
@@ -662,8 +510,6 @@ int set_texture(pbr_context* ctx, pbr_context::Texture& t, const void* texels, b
     return PBR_OK;
 }
 
-bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 int shade(pbr_context* ctx, const pbr_gbuffer_soa* gb, const pbr_frame_desc* fr, void* stream) {
     if (!ctx || !gb || !fr) return PBR_ERR_INVALID_ARGUMENT;
     if (gb->width < 0 || gb->height < 0 || gb->row_stride < gb->width || fr->out_row_stride < gb->width)
@@ -673,7 +519,7 @@ int shade(pbr_context* ctx, const pbr_gbuffer_soa* gb, const pbr_frame_desc* fr,
     // Everything below reads context state that pbr_set_pass / pbr_set_*_map write under the same
     // mutex: the launch arguments are built (and the kernel queued) in one critical section, so a
     // concurrent set_pass can never tear them.
-    std::lock_guard<std::mutex> lk(ctx->mu);
+    Entry en(ctx);
     if (!ctx->pass_set) return PBR_ERR_NOT_READY;
     if (gb->width == 0 || gb->height == 0) return PBR_OK;  // empty frame: nothing is read or written
     if (!fr->out) return PBR_ERR_INVALID_ARGUMENT;
@@ -744,12 +590,10 @@ int shade(pbr_context* ctx, const pbr_gbuffer_soa* gb, const pbr_frame_desc* fr,
                     : a.ps.faithful == 0 && !a.exact_only && a.ps.n_dir == 0 && ctx->points_quarter_ok ? 2
                                                                            : 0;
 
-    DeviceGuard g(ctx->device);
-    if (!g.ok) return PBR_ERR_NO_DEVICE;
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (const int rc = en.open(stream, "shade stream")) return rc;
+    const hipStream_t s = en.s;
+    const int si = en.si;
     hipError_t e = hipSuccess;
-    const int si = stream_index(ctx, s, e);
-    if (si < 0) return fail_hip(ctx, e, "shade stream");
     StreamState& st = ctx->streams[si];
     {
         const int64_t tiles = pbr::shade_tile_count(gb->width, gb->height, a.pixels_per_thread);
@@ -783,10 +627,7 @@ int shade(pbr_context* ctx, const pbr_gbuffer_soa* gb, const pbr_frame_desc* fr,
     e = pbr::launch_shade(a, s);
     if (e != hipSuccess) return fail_hip(ctx, e, "shade_tile_kernel launch", PBR_ERR_LAUNCH);
     st.kernel = pbr::launched_kernel(a);
-    if (ctx->streams.size() > 1) {
-        e = hipEventRecord(st.last_pass, s);
-        if (e != hipSuccess) return fail_hip(ctx, e, "shade record");
-    }
+    if (const int rc = after_launch(ctx, si, s, "shade record")) return rc;
     ctx->last_stream = si;
     return PBR_OK;
 }
@@ -830,471 +671,28 @@ int pbr_shade_frame(pbr_context* ctx, const pbr_gbuffer_soa* gb, const pbr_frame
 
 }  // extern "C"
 
-// ---- Material resolve (Default.hlsl:50-116 on the device; material_resolve.h) ----------------------------------------
-
-extern "C" {
-
-int pbr_set_materials(pbr_context* ctx, const pbr_material* materials, int32_t n_materials,
-                      const pbr_texture_desc* textures, int32_t n_textures, void* stream) {
-    if (!ctx || n_materials < 0 || n_materials >= (int32_t)PBR_MATERIAL_NONE || n_textures < 0)
-        return PBR_ERR_INVALID_ARGUMENT;
-    if ((n_materials > 0 && !materials) || (n_textures > 0 && !textures)) return PBR_ERR_INVALID_ARGUMENT;
-    // Texture placement in the one RGBA8 buffer; per texture at most 2^26 texels (as the env maps), 2^28 in all.
-    std::vector<pbr::MaterialTex> place((size_t)n_textures);
-    int64_t total = 0;
-    for (int32_t i = 0; i < n_textures; ++i) {
-        const pbr_texture_desc& t = textures[i];
-        if (!t.texels || t.width <= 0 || t.height <= 0) return PBR_ERR_INVALID_ARGUMENT;
-        if (t.channels != 1 && t.channels != 3 && t.channels != 4) return PBR_ERR_INVALID_ARGUMENT;
-        const int64_t n = (int64_t)t.width * t.height;
-        if (n > (1ll << 26) || total + n > (1ll << 28)) return PBR_ERR_INVALID_ARGUMENT;
-        place[(size_t)i] = pbr::MaterialTex{(uint32_t)total, t.width, t.height};
-        total += n;
-    }
-    constexpr uint32_t known = PBR_MAT_DIFFUSE_TEXTURE | PBR_MAT_SPECULAR_TEXTURE | PBR_MAT_METALLIC_TEXTURE |
-                               PBR_MAT_ROUGHNESS_TEXTURE | PBR_MAT_NORMAL_TEXTURE | PBR_MAT_ALPHA_TEST;
-    // tex[] slot of each flag bit: g_TextureArray 0 diffuse, 1 specular, 2 metallic, 3 roughness, 4 normal, 11 opacity
-    static const int slot_of_bit[6] = {0, 1, 2, 3, 4, 5};
-    std::vector<pbr::MaterialRec> recs((size_t)(n_materials > 0 ? n_materials : 1));
-    std::memset(recs.data(), 0, sizeof(pbr::MaterialRec) * recs.size());
-    for (int32_t i = 0; i < n_materials; ++i) {
-        const pbr_material& m = materials[i];
-        if (m.flags & ~known) return PBR_ERR_INVALID_ARGUMENT;
-        pbr::MaterialRec& r = recs[(size_t)i];
-        for (int c = 0; c < 3; ++c) r.diffuse[c] = m.diffuse_albedo[c], r.fresnel[c] = m.fresnel_r0[c];
-        r.metallic = m.metallic;
-        r.roughness = m.roughness;
-        r.opacity = m.opacity;
-        r.flags = m.flags;
-        for (int k = 0; k < 6; ++k) r.tex[k] = pbr::MaterialTex{0u, 1, 1};
-        for (int b = 0; b < 6; ++b) {
-            if (!(m.flags & (1u << b))) continue;
-            const int32_t t = m.tex[slot_of_bit[b]];
-            if (t < 0 || t >= n_textures) return PBR_ERR_INVALID_ARGUMENT;
-            r.tex[slot_of_bit[b]] = place[(size_t)t];
-        }
-    }
-    // Repack to RGBA8: one aligned dword per tap whatever the channel count; a gray texture replicates .r.
-    std::vector<uint32_t> texels((size_t)(total > 0 ? total : 1), 0u);
-    for (int32_t i = 0; i < n_textures; ++i) {
-        const pbr_texture_desc& t = textures[i];
-        uint32_t* dst = texels.data() + place[(size_t)i].offset;
-        const size_t n = (size_t)t.width * (size_t)t.height;
-        for (size_t k = 0; k < n; ++k) {
-            const uint8_t* p = t.texels + k * (size_t)t.channels;
-            const uint32_t r = p[0], g = t.channels == 1 ? p[0] : p[1], b = t.channels == 1 ? p[0] : p[2],
-                           a = t.channels == 4 ? p[3] : 255u;
-            dst[k] = r | (g << 8) | (b << 16) | (a << 24);
-        }
-    }
-
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard g(ctx->device);
-    if (!g.ok) return PBR_ERR_NO_DEVICE;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipError_t e = hipSuccess;
-    const int si = stream_index(ctx, s, e);
-    if (si < 0) return fail_hip(ctx, e, "pbr_set_materials stream");
-    pbr_context::Materials& mt = ctx->mats;
-    // The old table and texels may still be read by queued resolves: released after them, in stream order.
-    e = free_after_readers(ctx, mt.use, mt.d_table, s, si);
-    if (e == hipSuccess && mt.d_texels) e = hipFreeAsync(mt.d_texels, s);
-    if (e != hipSuccess) return fail_hip(ctx, e, "pbr_set_materials release");
-    mt.d_table = nullptr;
-    mt.d_texels = nullptr;
-    mt.set = false;
-    e = hipMallocAsync(reinterpret_cast<void**>(&mt.d_table), sizeof(pbr::MaterialRec) * recs.size(), s);
-    if (e == hipSuccess) e = hipMallocAsync(reinterpret_cast<void**>(&mt.d_texels), sizeof(uint32_t) * texels.size(), s);
-    if (e != hipSuccess) return fail_hip(ctx, e, "pbr_set_materials hipMalloc");
-    e = hipMemcpyAsync(mt.d_table, recs.data(), sizeof(pbr::MaterialRec) * recs.size(), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(mt.d_texels, texels.data(), sizeof(uint32_t) * texels.size(), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);  // the staging copies above are released on return
-    if (e != hipSuccess) return fail_hip(ctx, e, "pbr_set_materials copy");
-    mt.use.writer = -1;  // complete: later resolves on any stream see the new table
-    mt.n = n_materials;
-    mt.n_texels = (int64_t)texels.size();
-    mt.set = true;
-    return PBR_OK;
-}
-
-int pbr_resolve_materials(pbr_context* ctx, const pbr_attributes_soa* at, const pbr_gbuffer_targets* tg, int32_t filter,
-                          void* stream) {
-    if (!ctx || !at || !tg) return PBR_ERR_INVALID_ARGUMENT;
-    if (at->width < 0 || at->height < 0 || at->row_stride < at->width || tg->row_stride < at->width)
-        return PBR_ERR_INVALID_ARGUMENT;
-    if (filter != PBR_FILTER_POINT && filter != PBR_FILTER_LINEAR) return PBR_ERR_INVALID_ARGUMENT;
-    if (tg->coverage && tg->coverage_row_stride < at->width) return PBR_ERR_INVALID_ARGUMENT;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    if (!ctx->mats.set) return PBR_ERR_NOT_READY;
-    if (at->width == 0 || at->height == 0) return PBR_OK;  // empty frame: nothing is read or written
-    pbr::ResolveArgs a{};
-    const float* in[14] = {at->pos_w[0],     at->pos_w[1],     at->pos_w[2],       at->normal_w[0],    at->normal_w[1],
-                           at->normal_w[2],  at->tangent_w[0], at->tangent_w[1],   at->tangent_w[2],   at->bitangent_w[0],
-                           at->bitangent_w[1], at->bitangent_w[2], at->tex_coord[0], at->tex_coord[1]};
-    a.vec = (at->row_stride % 2) == 0 && (tg->row_stride % 2) == 0;
-    for (int i = 0; i < 14; ++i) {
-        if (!in[i] || !aligned(in[i], 4)) return PBR_ERR_INVALID_ARGUMENT;
-        a.attr[i] = in[i];
-        a.vec = a.vec && aligned(in[i], 8);
-    }
-    if (!at->material || !aligned(at->material, 2)) return PBR_ERR_INVALID_ARGUMENT;
-    a.material = at->material;
-    a.vec = a.vec && aligned(at->material, 4);
-    for (int i = 0; i < 15; ++i) {
-        if (!tg->planes[i] || !aligned(tg->planes[i], 4)) return PBR_ERR_INVALID_ARGUMENT;
-        a.plane[i] = tg->planes[i];
-        a.vec = a.vec && aligned(tg->planes[i], 8);
-    }
-    if (tg->opacity && !aligned(tg->opacity, 4)) return PBR_ERR_INVALID_ARGUMENT;
-    a.opacity = tg->opacity;
-    a.coverage = tg->coverage;
-    a.vec = a.vec && aligned(tg->opacity, 8) && aligned(tg->coverage, 2) &&
-            (!tg->coverage || (tg->coverage_row_stride % 2) == 0);
-    a.width = at->width;
-    a.height = at->height;
-    a.in_stride = at->row_stride;
-    a.out_stride = tg->row_stride;
-    a.cov_stride = tg->coverage ? tg->coverage_row_stride : 0;
-    a.table = ctx->mats.d_table;
-    a.n_materials = ctx->mats.n;
-    a.texels = ctx->mats.d_texels;
-    a.n_texels = ctx->mats.n_texels;
-    a.linear = filter == PBR_FILTER_LINEAR;
-
-    DeviceGuard g(ctx->device);
-    if (!g.ok) return PBR_ERR_NO_DEVICE;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipError_t e = hipSuccess;
-    const int si = stream_index(ctx, s, e);
-    if (si < 0) return fail_hip(ctx, e, "pbr_resolve_materials stream");
-    e = before_read(ctx->mats.use, s, si);
-    if (e != hipSuccess) return fail_hip(ctx, e, "pbr_resolve_materials order");
-    e = pbr::launch_resolve_materials(a, s);
-    if (e != hipSuccess) return fail_hip(ctx, e, "resolve_materials_kernel launch", PBR_ERR_LAUNCH);
-    // Not a shading pass: the stream's statistics record, its kernel name and the context's last pass stay as they
-    // are; only the event that orders a later pbr_set_materials after this read is recorded.
-    if (ctx->streams.size() > 1) {
-        e = hipEventRecord(ctx->streams[si].last_pass, s);
-        if (e != hipSuccess) return fail_hip(ctx, e, "pbr_resolve_materials record");
-    }
-    return PBR_OK;
-}
-
-}  // extern "C"
-
-// ---- Rasteriser (VS + the fixed-function rasteriser on the device; raster.h) --------------------------
-
 namespace {
 
-constexpr int32_t kRasterMaxSide = 32768;  // frame width and height: keeps every block and pixel count inside 32 bits
-
-size_t align_up(size_t n, size_t a) { return (n + a - 1) / a * a; }
-
-// The calling stream's pinned staging with room for `bytes`, free to be written: waits (on the host) for the upload
-// that last read it.
-hipError_t raster_staging(StreamState::Raster& r, size_t bytes) {
-    hipError_t e = hipSuccess;
-    if (r.staged_pending) {
-        e = hipEventSynchronize(r.staged);
-        if (e != hipSuccess) return e;
-        r.staged_pending = false;
-    }
-    if (!r.staged) {
-        e = hipEventCreateWithFlags(&r.staged, hipEventDisableTiming);
-        if (e != hipSuccess) return e;
-    }
-    if (bytes > r.h_capacity) {
-        if (r.h) (void)hipHostFree(r.h);
-        r.h = nullptr;
-        r.h_capacity = 0;
-        const size_t cap = align_up(bytes + bytes / 2, 4096);
-        e = hipHostMalloc(reinterpret_cast<void**>(&r.h), cap, hipHostMallocDefault);
-        if (e != hipSuccess) return e;
-        r.h_capacity = cap;
-    }
-    return hipSuccess;
-}
-
-}  // namespace
-
-extern "C" {
-
-int pbr_set_meshes(pbr_context* ctx, const pbr_mesh_desc* meshes, int32_t n_meshes, void* stream) {
-    if (!ctx || n_meshes < 0 || (n_meshes > 0 && !meshes)) return PBR_ERR_INVALID_ARGUMENT;
-    std::vector<pbr_context::MeshPlace> place((size_t)n_meshes);
-    int64_t nv = 0, ni = 0;
-    for (int32_t i = 0; i < n_meshes; ++i) {
-        const pbr_mesh_desc& m = meshes[i];
-        if (m.n_vertices < 0 || m.n_indices < 0) return PBR_ERR_INVALID_ARGUMENT;
-        if ((m.n_vertices > 0 && !m.vertices) || (m.n_indices > 0 && !m.indices)) return PBR_ERR_INVALID_ARGUMENT;
-        for (int32_t k = 0; k < m.n_indices; ++k)
-            if (m.indices[k] >= (uint32_t)m.n_vertices) return PBR_ERR_INVALID_ARGUMENT;
-        place[(size_t)i] = pbr_context::MeshPlace{(uint32_t)nv, (uint32_t)m.n_vertices, (uint32_t)ni, (uint32_t)m.n_indices};
-        nv += m.n_vertices;
-        ni += m.n_indices;
-        if (nv > (1ll << 27) || ni > (1ll << 31)) return PBR_ERR_INVALID_ARGUMENT;  // 7.5 GB of vertices, 8 GB of indices
-    }
-    std::vector<float> vertices((size_t)(nv > 0 ? nv * 14 : 1), 0.0f);
-    std::vector<uint32_t> indices((size_t)(ni > 0 ? ni : 1), 0u);
-    for (int32_t i = 0; i < n_meshes; ++i) {
-        const pbr_mesh_desc& m = meshes[i];
-        if (m.n_vertices > 0)
-            std::memcpy(vertices.data() + (size_t)place[(size_t)i].vtx_base * 14, m.vertices,
-                        sizeof(float) * 14 * (size_t)m.n_vertices);
-        if (m.n_indices > 0)
-            std::memcpy(indices.data() + place[(size_t)i].idx_base, m.indices, sizeof(uint32_t) * (size_t)m.n_indices);
-    }
-
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard g(ctx->device);
-    if (!g.ok) return PBR_ERR_NO_DEVICE;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipError_t e = hipSuccess;
-    const int si = stream_index(ctx, s, e);
-    if (si < 0) return fail_hip(ctx, e, "pbr_set_meshes stream");
-    pbr_context::Meshes& ms = ctx->meshes;
-    // The old buffers may still be read by queued rasterisations: released after them, in stream order.
-    e = free_after_readers(ctx, ms.use, ms.d_vertices, s, si);
-    if (e == hipSuccess && ms.d_indices) e = hipFreeAsync(ms.d_indices, s);
-    if (e != hipSuccess) return fail_hip(ctx, e, "pbr_set_meshes release");
-    ms.d_vertices = nullptr;
-    ms.d_indices = nullptr;
-    ms.set = false;
-    e = hipMallocAsync(reinterpret_cast<void**>(&ms.d_vertices), sizeof(float) * vertices.size(), s);
-    if (e == hipSuccess) e = hipMallocAsync(reinterpret_cast<void**>(&ms.d_indices), sizeof(uint32_t) * indices.size(), s);
-    if (e != hipSuccess) return fail_hip(ctx, e, "pbr_set_meshes hipMalloc");
-    e = hipMemcpyAsync(ms.d_vertices, vertices.data(), sizeof(float) * vertices.size(), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(ms.d_indices, indices.data(), sizeof(uint32_t) * indices.size(), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);  // the staging copies above are released on return
-    if (e != hipSuccess) return fail_hip(ctx, e, "pbr_set_meshes copy");
-    ms.use.writer = -1;  // complete: later rasterisations on any stream see the new set
-    ms.n_vertices = nv;
-    ms.n_indices = ni;
-    ms.place = std::move(place);
-    ms.set = true;
-    return PBR_OK;
-}
-
-}  // extern "C"
-
-namespace {
-
-// pbr_rasterize. `marks` (development, pbr_debug_rasterize_timed): six events recorded around the five stages --
-// clears and table upload, vertex transform, setup with the small triangles' coverage, large triangles, resolve.
-int rasterize_impl(pbr_context* ctx, const pbr_draw* draws, int32_t n_draws, const pbr_raster_view* view,
-                   const pbr_raster_targets* tg, void* stream, hipEvent_t* marks) {
-    if (!ctx || !view || !tg || n_draws < 0 || (n_draws > 0 && !draws)) return PBR_ERR_INVALID_ARGUMENT;
-    if (view->width < 0 || view->height < 0 || view->width > kRasterMaxSide || view->height > kRasterMaxSide)
-        return PBR_ERR_INVALID_ARGUMENT;
-    if (view->row_begin < 0 || view->row_begin > view->row_end || view->row_end > view->height)
-        return PBR_ERR_INVALID_ARGUMENT;
-    if (tg->row_stride < view->width) return PBR_ERR_INVALID_ARGUMENT;
-    for (int32_t i = 0; i < n_draws; ++i) {
-        const pbr_draw& d = draws[i];
-        if (d.mesh < 0 || d.first_index < 0 || d.index_count < 0 || d.index_count % 3 != 0 || d.cull > 1)
-            return PBR_ERR_INVALID_ARGUMENT;
-    }
-    pbr::RasterArgs a{};
-    a.vec = (tg->row_stride % 2) == 0;
-    for (int i = 0; i < 14; ++i) {
-        if (!tg->planes[i] || !aligned(tg->planes[i], 4)) return PBR_ERR_INVALID_ARGUMENT;
-        a.plane[i] = tg->planes[i];
-        a.vec = a.vec && aligned(tg->planes[i], 8);
-    }
-    if (!tg->material || !aligned(tg->material, 2)) return PBR_ERR_INVALID_ARGUMENT;
-    if (tg->depth && !aligned(tg->depth, 4)) return PBR_ERR_INVALID_ARGUMENT;
-    a.material = tg->material;
-    a.depth = tg->depth;
-    a.vec = a.vec && aligned(tg->material, 4) && aligned(tg->depth, 8);
-    a.stride = tg->row_stride;
-    a.width = view->width;
-    a.height = view->height;
-    a.row_begin = view->row_begin;
-    a.row_end = view->row_end;
-    std::memcpy(a.view_proj, view->view_proj, sizeof(a.view_proj));
-    for (int c = 0; c < 3; ++c)
-        a.eye[c] = view->eye[c], a.right[c] = view->bg_right[c], a.up[c] = view->bg_up[c], a.fwd[c] = view->bg_forward[c];
-
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    const pbr_context::Meshes& ms = ctx->meshes;
-    if (!ms.set) return PBR_ERR_NOT_READY;
-    uint64_t n_tris = 0, n_records = 0;
-    for (int32_t i = 0; i < n_draws; ++i) {
-        const pbr_draw& d = draws[i];
-        if ((size_t)d.mesh >= ms.place.size()) return PBR_ERR_INVALID_ARGUMENT;
-        const pbr_context::MeshPlace& mp = ms.place[(size_t)d.mesh];
-        if ((uint64_t)d.first_index + (uint64_t)d.index_count > (uint64_t)mp.n_indices) return PBR_ERR_INVALID_ARGUMENT;
-        n_tris += (uint64_t)d.index_count / 3u;
-        n_records += mp.n_vertices;
-    }
-    if (n_tris > 0xFFFFFFFEull || n_records > 0x7FFFFFFFull) return PBR_ERR_INVALID_ARGUMENT;
-    const int band_h = view->row_end - view->row_begin;
-    if (view->width == 0 || band_h == 0) return PBR_OK;  // an empty band: nothing is read or written
-
-    DeviceGuard g(ctx->device);
-    if (!g.ok) return PBR_ERR_NO_DEVICE;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipError_t e = hipSuccess;
-    const int si = stream_index(ctx, s, e);
-    if (si < 0) return fail_hip(ctx, e, "pbr_rasterize stream");
-    StreamState::Raster& rs = ctx->streams[si].raster;
-
-    // The draw table: the records, then the triangle and vertex-record prefixes.
-    const size_t nd = (size_t)n_draws;
-    const size_t table_bytes = sizeof(pbr::RasterDraw) * nd + sizeof(uint32_t) * 2 * (nd + 1);
-    e = raster_staging(rs, table_bytes);
-    if (e != hipSuccess) return fail_hip(ctx, e, "pbr_rasterize staging");
-    pbr::RasterDraw* h_draws = reinterpret_cast<pbr::RasterDraw*>(rs.h);
-    uint32_t* h_tri = reinterpret_cast<uint32_t*>(rs.h + sizeof(pbr::RasterDraw) * nd);
-    uint32_t* h_rec = h_tri + (nd + 1);
-    uint32_t tri = 0, rec = 0;
-    for (size_t i = 0; i < nd; ++i) {
-        const pbr_draw& d = draws[i];
-        const pbr_context::MeshPlace& mp = ms.place[(size_t)d.mesh];
-        pbr::RasterDraw& r = h_draws[i];
-        std::memcpy(r.world, d.world, sizeof(r.world));
-        std::memcpy(r.tex, d.tex_transform, sizeof(r.tex));
-        std::memcpy(r.mat, d.mat_transform, sizeof(r.mat));
-        r.vtx_src = mp.vtx_base;
-        r.idx_src = mp.idx_base + (uint32_t)d.first_index;
-        r.rec_base = rec;
-        r.n_vertices = mp.n_vertices;
-        r.material = d.material;
-        r.cull = d.cull;
-        r.pad[0] = r.pad[1] = 0u;
-        h_tri[i] = tri;
-        h_rec[i] = rec;
-        tri += (uint32_t)d.index_count / 3u;
-        rec += mp.n_vertices;
-    }
-    h_tri[nd] = tri;
-    h_rec[nd] = rec;
-
-    // Device scratch of this stream: counters | draw table | vertex records | large list | visibility words.
-    const size_t off_table = 256;
-    const size_t off_records = off_table + align_up(table_bytes, 256);
-    const size_t off_large = off_records + align_up(sizeof(pbr::RasterVertex) * (size_t)n_records, 256);
-    const size_t off_vis = off_large + align_up(sizeof(uint2) * (size_t)n_tris, 256);
-    const size_t vis_bytes = sizeof(unsigned long long) * (size_t)band_h * (size_t)view->width;
-    const size_t need = off_vis + vis_bytes;
-    if (need > rs.capacity) {  // grown in stream order: the stream's earlier rasterisations finish with the old block
-        if (rs.d) {
-            e = hipFreeAsync(rs.d, s);
-            if (e != hipSuccess) return fail_hip(ctx, e, "pbr_rasterize release");
-        }
-        rs.d = nullptr;
-        rs.capacity = 0;
-        e = hipMallocAsync(reinterpret_cast<void**>(&rs.d), need, s);
-        if (e != hipSuccess) return fail_hip(ctx, e, "pbr_rasterize hipMalloc");
-        rs.capacity = need;
-    }
-    rs.d_counters = reinterpret_cast<unsigned long long*>(rs.d);
-    a.counters = rs.d_counters;
-    a.draws = reinterpret_cast<const pbr::RasterDraw*>(rs.d + off_table);
-    a.tri_prefix = reinterpret_cast<const uint32_t*>(rs.d + off_table + sizeof(pbr::RasterDraw) * nd);
-    a.rec_prefix = a.tri_prefix + (nd + 1);
-    a.records = reinterpret_cast<pbr::RasterVertex*>(rs.d + off_records);
-    a.large = reinterpret_cast<uint2*>(rs.d + off_large);
-    a.vis = reinterpret_cast<unsigned long long*>(rs.d + off_vis);
-    a.n_draws = n_draws;
-    a.n_tris = (uint32_t)n_tris;
-    a.n_records = (uint32_t)n_records;
-    a.vertices = ms.d_vertices;
-    a.indices = ms.d_indices;
-    a.n_src_vertices = ms.n_vertices;
-    a.n_src_indices = ms.n_indices;
-
-    e = before_read(ctx->meshes.use, s, si);
-    if (e != hipSuccess) return fail_hip(ctx, e, "pbr_rasterize order");
-    auto mark = [&](int i) { return marks ? hipEventRecord(marks[i], s) : hipSuccess; };
-    (void)mark(0);
-    e = hipMemsetAsync(rs.d, 0, sizeof(unsigned long long) * pbr::kRasterCounters, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(rs.d + off_table, rs.h, table_bytes, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipEventRecord(rs.staged, s);
-    if (e != hipSuccess) return fail_hip(ctx, e, "pbr_rasterize upload");
-    rs.staged_pending = true;
-    e = hipMemsetAsync(a.vis, 0xFF, vis_bytes, s);
-    if (e != hipSuccess) return fail_hip(ctx, e, "pbr_rasterize clear");
-    (void)mark(1);
-    e = pbr::launch_raster_vertices(a, s);
-    if (e != hipSuccess) return fail_hip(ctx, e, "raster_vertex_kernel launch", PBR_ERR_LAUNCH);
-    (void)mark(2);
-    e = pbr::launch_raster_setup(a, s);
-    if (e != hipSuccess) return fail_hip(ctx, e, "raster_setup_kernel launch", PBR_ERR_LAUNCH);
-    (void)mark(3);
-    e = pbr::launch_raster_large(a, s);
-    if (e != hipSuccess) return fail_hip(ctx, e, "raster_large_kernel launch", PBR_ERR_LAUNCH);
-    (void)mark(4);
-    e = pbr::launch_raster_resolve(a, s);
-    if (e != hipSuccess) return fail_hip(ctx, e, "raster_resolve_kernel launch", PBR_ERR_LAUNCH);
-    (void)mark(5);
-    rs.triangles = (int64_t)n_tris;
-    rs.ran = true;
-    // Not a shading pass: the stream's statistics record and kernel name stay; only the event that orders a later
-    // pbr_set_meshes after this read is recorded.
-    if (ctx->streams.size() > 1) {
-        e = hipEventRecord(ctx->streams[si].last_pass, s);
-        if (e != hipSuccess) return fail_hip(ctx, e, "pbr_rasterize record");
-    }
-    return PBR_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int pbr_rasterize(pbr_context* ctx, const pbr_draw* draws, int32_t n_draws, const pbr_raster_view* view,
-                  const pbr_raster_targets* targets, void* stream) {
-    return rasterize_impl(ctx, draws, n_draws, view, targets, stream, nullptr);
-}
-
-int pbr_last_raster_stats(pbr_context* ctx, pbr_raster_stats* out, void* stream) {
-    if (!ctx || !out) return PBR_ERR_INVALID_ARGUMENT;
-    *out = pbr_raster_stats{};
-    DeviceGuard g(ctx->device);
-    if (!g.ok) return PBR_ERR_NO_DEVICE;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const StreamState* st = nullptr;
-    for (const StreamState& c : ctx->streams)
-        if (c.stream == s && c.raster.ran) st = &c;
-    if (!st) return PBR_OK;
-    unsigned long long h[pbr::kRasterCounters] = {};
-    hipError_t e = hipMemcpyAsync(h, st->raster.d_counters, sizeof(h), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return fail_hip(ctx, e, "pbr_last_raster_stats");
-    out->triangles = st->raster.triangles;
-    out->backface_culled = (int64_t)h[pbr::kRasterCulled];
-    out->zero_area = (int64_t)h[pbr::kRasterZeroArea];
-    out->skipped_near = (int64_t)h[pbr::kRasterNear];
-    out->skipped_guard_band = (int64_t)h[pbr::kRasterGuard];
-    out->fragments = (int64_t)h[pbr::kRasterFragments];
-    return PBR_OK;
-}
-
-}  // extern "C"
-
-namespace {
-
-// Sum the statistics records of the last pass on `stream` (or, if the context never launched on that stream,
-// of its last pass on any stream: the caller's stream is then ordered after it by contract).
-int sum_pass_stats(pbr_context* ctx, pbr_pass_stats* out, void* stream, const char* what) {
-    *out = pbr_pass_stats{};
-    DeviceGuard g(ctx->device);
-    if (!g.ok) return PBR_ERR_NO_DEVICE;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    hipStream_t s = static_cast<hipStream_t>(stream);
+// The StreamState index of the last pass on `s` or, if the context never launched on that stream, of its last pass on
+// any stream (the caller's stream is then ordered after it by contract); -1: none.
+int pass_stream(const pbr_context* ctx, hipStream_t s) {
     int si = -1;
     for (size_t i = 0; i < ctx->streams.size(); ++i)
         if (ctx->streams[i].stream == s && ctx->streams[i].tiles > 0) si = (int)i;
-    if (si < 0) si = ctx->last_stream;
+    return si < 0 ? ctx->last_stream : si;
+}
+
+// Sum the statistics records of that pass.
+int sum_pass_stats(pbr_context* ctx, pbr_pass_stats* out, void* stream, const char* what) {
+    *out = pbr_pass_stats{};
+    Entry en(ctx);
+    if (const int rc = en.device(stream)) return rc;
+    const int si = pass_stream(ctx, en.s);
     if (si < 0 || ctx->streams[si].tiles == 0) return PBR_OK;  // no pass yet (or an empty frame)
     const StreamState& st = ctx->streams[si];
     std::vector<int32_t> h(pbr::kStatsPerBlock * (size_t)st.slots);
-    hipError_t e = hipMemcpyAsync(h.data(), st.d_stats, sizeof(int32_t) * h.size(), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    hipError_t e = hipMemcpyAsync(h.data(), st.d_stats, sizeof(int32_t) * h.size(), hipMemcpyDeviceToHost, en.s);
+    if (e == hipSuccess) e = hipStreamSynchronize(en.s);
     if (e != hipSuccess) return fail_hip(ctx, e, what);
     out->workgroups = st.tiles;
     out->culled = st.culled ? 1 : 0;
@@ -1333,11 +731,7 @@ int pbr_last_pass_stats(pbr_context* ctx, pbr_pass_stats* out, void* stream) {
 const char* pbr_last_pass_kernel(pbr_context* ctx, void* stream) {
     if (!ctx) return "";
     std::lock_guard<std::mutex> lk(ctx->mu);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    int si = -1;
-    for (size_t i = 0; i < ctx->streams.size(); ++i)
-        if (ctx->streams[i].stream == s && ctx->streams[i].tiles > 0) si = (int)i;
-    if (si < 0) si = ctx->last_stream;
+    const int si = pass_stream(ctx, static_cast<hipStream_t>(stream));
     return si < 0 ? "" : ctx->streams[si].kernel.c_str();
 }
 
@@ -1362,29 +756,6 @@ int pbr_debug_bounds(pbr_context* ctx, uint32_t* flags, int reset) {
 }
 
 }  // extern "C"
-
-// Development (tools/raster_bench.py; not in the public header): one pbr_rasterize with HIP events between its stages;
-// synchronises `stream` and writes the milliseconds of the clears and table upload, the vertex transform, the setup
-// with the small triangles' coverage, the large triangles' coverage and the per-pixel resolve into ms5.
-extern "C" int pbr_debug_rasterize_timed(pbr_context* ctx, const pbr_draw* draws, int32_t n_draws,
-                                         const pbr_raster_view* view, const pbr_raster_targets* targets, void* stream,
-                                         float* ms5) {
-    if (!ctx || !ms5) return PBR_ERR_INVALID_ARGUMENT;
-    DeviceGuard g(ctx->device);
-    if (!g.ok) return PBR_ERR_NO_DEVICE;
-    hipEvent_t ev[6] = {};
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < 6 && e == hipSuccess; ++i) e = hipEventCreate(&ev[i]);
-    int rc = e == hipSuccess ? rasterize_impl(ctx, draws, n_draws, view, targets, stream, ev) : PBR_ERR_HIP;
-    if (rc == PBR_OK && hipStreamSynchronize(static_cast<hipStream_t>(stream)) != hipSuccess) rc = PBR_ERR_HIP;
-    for (int i = 0; i < 5; ++i) {
-        ms5[i] = 0.0f;
-        if (rc == PBR_OK && hipEventElapsedTime(&ms5[i], ev[i], ev[i + 1]) != hipSuccess) rc = PBR_ERR_HIP;
-    }
-    for (hipEvent_t x : ev)
-        if (x) (void)hipEventDestroy(x);
-    return rc;
-}
 
 // Development: the balanced pass's per-phase clock sums of a PBR_BAL_PROFILE build (not in the public header).
 extern "C" int pbr_debug_bal_profile(unsigned long long* out8, int reset) {

@@ -1,8 +1,7 @@
 // raster.h -- VS (Default.hlsl:22-45) and the rasteriser behind DrawIndexedInstanced (PBRApp.cpp:1133) on the device:
 // indexed triangle lists in, the 14 planes of a pbr_attributes_soa, the material plane and the depth plane out
-// (pbr_rasterize, include/pbr/pbr_shade.h; DESIGN.md §12 fixes every operation). Included by shade_kernels.hip (its
-// !PBR_BAL_TU part), so it is compiled with that unit's canonical fp32 flags: no contraction, correctly rounded / and
-// sqrt.
+// (pbr_rasterize, include/pbr/pbr_shade.h; DESIGN.md §12 fixes every operation). A source of frontend_kernels.hip, which
+// is compiled with the canonical fp32 flags: no contraction, correctly rounded / and sqrt.
 //
 // Four launches, stream-ordered, none waiting on another workgroup:
 //   1. raster_vertex_kernel: one lane per (draw, vertex): VS, the perspective division, the viewport and the snap
@@ -22,7 +21,7 @@
 #pragma once
 
 #include "pbr_device_math.h"
-#include "shade_kernels.h"
+#include "frontend_kernels.h"
 
 namespace pbr {
 

@@ -1771,14 +1771,6 @@ hipError_t launch_decode_unorm16(const uint16_t* src, float4* dst, int n_texels,
 
 }  // namespace pbr
 
-#if !PBR_BAL_TU
-// The material resolve kernel (pbr_resolve_materials) lives in this unit beside decode_unorm16_kernel: same FP flags,
-// same build record, same bounds-flag buffer.
-#include "material_resolve.h"
-// So do the rasteriser's kernels (pbr_rasterize), which produce the attributes that kernel consumes.
-#include "raster.h"
-#endif
-
 // This unit's build record (pbr_build_info.h, pbr_build_info): the stamp, flavor and flags it was compiled with and
 // every build switch of the kernels as the preprocessor saw it.
 #include "pbr_build_info.h"

@@ -28,7 +28,7 @@ LAYOUTS = {"pair": {}, "px1": {"PBR_PIXELS_PER_THREAD": "1"}, "nolean": {"PBR_LE
 DEBUG_LIB = os.path.join(ROOT, "physically_based_renderer_amd", "_lib", "debug_bounds", "libpbrshade.so")
 DEBUG_FLAVOR = "debug_bounds"
 # The units `make debug-bounds` compiles with -DPBR_DEBUG_BOUNDS=1; the G-buffer fill is the product object (host code).
-DEBUG_UNITS = ("shade_kernels", "shade_kernels_bal", "pbr_context")
+DEBUG_UNITS = ("shade_kernels", "shade_kernels_bal", "frontend_kernels", "pbr_context", "pbr_frontend")
 
 
 def library_build_info(lib_path: str) -> dict:

@@ -216,7 +216,7 @@ def main(out_path):
         flagged = ctx.debug_bounds()
         result["bounds"] = np.array([flagged.get(k, -1) for k in ("gbuffer", "output", "coverage", "texel", "light",
                                                                   "lds", "raster", "mesh")], np.int64)
-    unit = next(u for u in N.build_info()["units"] if u["unit"] == "shade_kernels")  # the raster kernels' unit
+    unit = next(u for u in N.build_info()["units"] if u["unit"] == "frontend_kernels")  # the raster kernels' unit
     result["flavor"], result["sources_sha"] = np.array(unit["flavor"]), np.array(unit["sources_sha"])
     np.savez(out_path, **result)
     print("rasterize under", N.LIB_PATH, "bounds", flagged)

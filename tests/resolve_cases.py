@@ -149,7 +149,7 @@ def main(out_path):
         flagged = ctx.debug_bounds()
         result["bounds"] = np.array([flagged.get(k, -1) for k in ("gbuffer", "output", "coverage", "texel", "light",
                                                                   "lds")], np.int64)
-    unit = next(u for u in N.build_info()["units"] if u["unit"] == "shade_kernels")  # the resolve kernel's unit
+    unit = next(u for u in N.build_info()["units"] if u["unit"] == "frontend_kernels")  # the resolve kernel's unit
     result["flavor"], result["sources_sha"] = np.array(unit["flavor"]), np.array(unit["sources_sha"])
     np.savez(out_path, **result)
     print("resolve under", N.LIB_PATH, "bounds", flagged)

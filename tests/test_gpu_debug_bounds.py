@@ -5,8 +5,9 @@ layer (d3dApp.cpp:443-444); GPU AddressSanitizer is not available on this pool.
 
 Bars: no index class is ever flagged; every frame is bit-identical to the product library's (a redirected index
 would change it); the build's checks do fire -- PBR_DEBUG_BOUNDS_SKEW=1 narrows the output extent the checks use
-by one column and must flag class "output" on every pass. The debug library runs in a child process (one library
-per process; PBR_LIB_PATH)."""
+by one column and must flag class "output" on every pass, and hands the front end's checks an index count and a texel
+count of 0, which must flag "mesh" and "texel" (the front end's kernels are a unit of their own, with their own flag
+pointer). The debug library runs in a child process (one library per process; PBR_LIB_PATH)."""
 import os
 import subprocess
 import sys
@@ -15,6 +16,7 @@ import numpy as np
 import pytest
 
 import bounds_cases
+import frontend_skew_cases
 
 pytestmark = pytest.mark.gpu
 
@@ -22,7 +24,7 @@ ROOT = bounds_cases.ROOT
 DEBUG_LIB = bounds_cases.DEBUG_LIB
 
 
-def _child(tmp_path, name, extra_env=None):
+def _child(tmp_path, name, extra_env=None, script="bounds_cases.py"):
     from physically_based_renderer_amd import _native as N
 
     if not os.path.exists(DEBUG_LIB):
@@ -34,7 +36,7 @@ def _child(tmp_path, name, extra_env=None):
                           + " (rebuild: make -C physically_based_renderer_amd/csrc debug-bounds)")
     out = tmp_path / f"{name}.npz"
     env = {**os.environ, "PBR_LIB_PATH": DEBUG_LIB, **(extra_env or {})}
-    r = subprocess.run([sys.executable, "-u", os.path.join(ROOT, "tests", "bounds_cases.py"), str(out)], env=env,
+    r = subprocess.run([sys.executable, "-u", os.path.join(ROOT, "tests", script), str(out)], env=env,
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     print(r.stdout.strip())
@@ -77,3 +79,14 @@ def test_debug_bounds_negative_control(tmp_path, gpu):
     assert bounds
     missed = [k for k, v in bounds.items() if v[1] < 0]
     assert not missed, f"output-extent skew not detected in {missed}"
+
+
+def test_debug_bounds_negative_control_front_end(tmp_path, gpu):
+    """The front end's kernel unit reports to the flag buffer too: under the skew one rasterisation (70x37) must flag
+    class "mesh" (every index read is checked against a count of 0) and one textured resolve (70x3) class "texel"
+    (every tap against 0 texels). Without the skew both stay clean (test_gpu_raster.py, test_gpu_resolve.py:
+    test_bounds_checked_build_is_clean_and_equal). Nothing is asserted about the pixels."""
+    dbg = _child(tmp_path, "skew_front_end", {"PBR_DEBUG_BOUNDS_SKEW": "1"}, script="frontend_skew_cases.py")
+    classes = frontend_skew_cases.CLASSES
+    assert dbg["rasterize"][classes.index("mesh")] >= 0, f"index-count skew not detected: {dbg['rasterize']}"
+    assert dbg["resolve"][classes.index("texel")] >= 0, f"texel-count skew not detected: {dbg['resolve']}"

@@ -23,13 +23,16 @@ HIPCC = "/opt/rocm/bin/hipcc"
 def test_the_in_tree_library_is_the_product_build_of_this_checkout():
     info = N.build_info()
     units = {u["unit"] for u in info["units"]}
-    assert units == {"pbr_context", "shade_kernels", "shade_kernels_bal", "gbuffer_fill"}
+    assert units == {"pbr_context", "pbr_frontend", "shade_kernels", "shade_kernels_bal", "frontend_kernels",
+                     "gbuffer_fill"}
     assert info["abi"] == N.lib().pbr_abi_version() == 9
     assert info["sources_sha"] == N.kernel_sources_sha() and info["flavor"] == N.PRODUCT_FLAVOR
     assert N.build_problems(info) == []
     sk = next(u for u in info["units"] if u["unit"] == "shade_kernels")
     assert sk["switches"]["PBR_X2_MIN_WAVES"] == "4" and sk["switches"]["PBR_DEBUG_BOUNDS"] == "0"
     assert "max-ilp" in sk["cflags"]  # the unit's own scheduler flag is recorded
+    fk = next(u for u in info["units"] if u["unit"] == "frontend_kernels")
+    assert "max-ilp" in fk["cflags"] and fk["switches"]["PBR_DEBUG_BOUNDS"] == "0"  # the front end keeps that scheduler
 
 
 def test_build_problems_name_each_kind_of_non_product_build():
@@ -49,16 +52,17 @@ def test_build_problems_name_each_kind_of_non_product_build():
 
 def _relink(tmp_path, name, defines):
     """The product objects with gbuffer_fill.cpp recompiled under `defines` (the fastest unit to rebuild)."""
-    if not all(os.path.exists(os.path.join(OBJ, f)) for f in ("shade_kernels.o", "shade_kernels_bal.o", "pbr_context.o")):
+    built = os.listdir(OBJ) if os.path.isdir(OBJ) else []
+    product = sorted(f for f in built if f.endswith(".o") and f != "gbuffer_fill.o")  # every unit the Makefile built
+    if not product:
         pytest.skip("product objects not built (build/obj)")
     obj = tmp_path / f"{name}_gbuffer_fill.o"
     so = tmp_path / name / "libpbrshade.so"
     so.parent.mkdir()
     subprocess.run([HIPCC, "-O1", "-std=c++17", "-fPIC", f"-I{ROOT}/include", f"-I{CSRC}", *defines, "-x", "c++", "-c",
                     os.path.join(CSRC, "gbuffer_fill.cpp"), "-o", str(obj)], check=True)
-    subprocess.run([HIPCC, "--offload-arch=gfx950", "-shared", "-o", str(so), os.path.join(OBJ, "shade_kernels.o"),
-                    os.path.join(OBJ, "shade_kernels_bal.o"), os.path.join(OBJ, "pbr_context.o"), str(obj),
-                    "-lpthread"], check=True)
+    subprocess.run([HIPCC, "--offload-arch=gfx950", "-shared", "-o", str(so), *(os.path.join(OBJ, f) for f in product),
+                    str(obj), "-lpthread"], check=True)
     return str(so)
 
 
@@ -110,7 +114,7 @@ def test_debug_bounds_comparison_refuses_a_restamped_or_product_library(tmp_path
     info = {"units": [{"unit": u, "sources_sha": "ffffffffffffffff", "flavor": B.DEBUG_FLAVOR} for u in B.DEBUG_UNITS]
             + [{"unit": "gbuffer_fill", "sources_sha": tree, "flavor": "product"}]}
     p = B.debug_library_problems(info, tree)
-    assert len(p) == 3 and all("ffffffffffffffff" in s for s in p)
+    assert len(p) == len(B.DEBUG_UNITS) == 5 and all("ffffffffffffffff" in s for s in p)
     if os.path.exists(B.DEBUG_LIB):
         info = B.library_build_info(B.DEBUG_LIB)
         if info["sources_sha"] == tree or all(u["sources_sha"] == tree for u in info["units"]):
@@ -122,6 +126,6 @@ def test_bench_records_the_loaded_library():
     lib = bench.library_provenance(False)
     assert lib["path"] == os.path.join("physically_based_renderer_amd", "_lib", "libpbrshade.so")
     assert lib["sources_sha"] == lib["tree_sources_sha"] == N.kernel_sources_sha()
-    assert lib["flavor"] == "product" and len(lib["units"]) == 4
+    assert lib["flavor"] == "product" and len(lib["units"]) == 6
     overrides = [k for k in os.environ if k.startswith("PBR_") and k not in bench.ENV_NEUTRAL]
     assert bool(lib["problems"]) == bool(overrides)
