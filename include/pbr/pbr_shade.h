@@ -345,8 +345,11 @@ int pbr_resolve_materials(pbr_context* ctx, const pbr_attributes_soa* attrs, con
  * PBRApp.cpp:793-795; CULL_MODE_NONE for the transparent, alpha-tested and sky PSOs, :843-859), on the device: indexed
  * triangle lists in, the planes of a pbr_attributes_soa out, which pbr_resolve_materials consumes (which
  * fixes the semantics operation by operation: top-left rule on an 8-bit subpixel grid, one sample per pixel, depth
- * test LESS against a buffer cleared to 1, perspective-correct attributes; no clipping against w = 0). Additive like
- * the resolve: PBR_ABI_VERSION stays 9, detect by symbol. */
+ * test LESS against a buffer cleared to 1, perspective-correct attributes). pbr_rasterize does not clip: a triangle with
+ * a vertex whose w is not > 0 is skipped whole. pbr_rasterize_flags with PBR_RASTER_CLIP_NEAR clips every triangle
+ * against the near plane z = 0 first, as the fixed-function pipeline does, so a floor under the eye, a wall beside it
+ * or a sphere around it are drawn; the far plane stays a per-fragment test. Additive like the
+ * resolve: PBR_ABI_VERSION stays 9, detect by symbol. */
 
 /* One mesh in HOST memory: vertices in the reference's `Vertex` order (FrameResource.h:46-52), 14 floats each (Pos 3,
  * Normal 3, Tangent 3, Bitangent 3, TexCoord 2), and a triangle list of 32-bit indices. */
@@ -415,7 +418,8 @@ typedef struct pbr_raster_stats {
     int64_t triangles;          /* submitted */
     int64_t backface_culled;    /* signed area < 0 under cull 0 */
     int64_t zero_area;          /* signed area == 0 on the subpixel grid */
-    int64_t skipped_near;       /* a vertex whose w is not > 0: not drawn (no clipping against w = 0) */
+    int64_t skipped_near;       /* a vertex whose w is not > 0: not drawn. Under PBR_RASTER_CLIP_NEAR: triangles with
+                                 * every vertex in front of z = 0, and triangles or pieces left with such a vertex */
     int64_t skipped_guard_band; /* a vertex beyond +-2^23 subpixels, or not finite: not drawn */
     int64_t fragments;          /* (triangle, pixel) pairs that passed coverage and 0 <= z < 1 */
 } pbr_raster_stats;
@@ -423,6 +427,29 @@ typedef struct pbr_raster_stats {
 /* The counters of the last pbr_rasterize on `stream` (synchronises `stream`, like pbr_last_cull_stats); zeros when
  * the context has not rasterised on that stream. */
 int pbr_last_raster_stats(pbr_context* ctx, pbr_raster_stats* out, void* stream);
+
+/* pbr_rasterize with options. flags == 0 is pbr_rasterize, bit for bit, statistics included.
+ * PBR_RASTER_CLIP_NEAR: a vertex is inside iff PosH.z >= 0 (NaN is outside, -0 inside). A triangle with three inside
+ * vertices is drawn as by pbr_rasterize; one with none is counted in skipped_near; one with 1 or 2 is cut at z = 0
+ * into 1 or 2 pieces, each new vertex computed along its edge from the inside end to the outside end (so that two
+ * triangles sharing a crossing edge get the identical vertex and the clipped mesh stays watertight). A piece is then a
+ * triangle like any other -- the w > 0 rule, viewport, guard band, area, culling, coverage and the counters of those
+ * names apply to it -- except that it keeps its source triangle's place in the equal-depth order; `triangles` counts
+ * source triangles, so triangles + clip_pieces - clipped_near = the triangles and pieces that reach coverage +
+ * backface_culled + zero_area + skipped_near + skipped_guard_band. Arguments, stream rules, errors and scratch as pbr_rasterize; an unknown flag bit, or more than
+ * 2^31 - 1 triangles in a clipping call: PBR_ERR_INVALID_ARGUMENT. */
+enum { PBR_RASTER_CLIP_NEAR = 1u << 0 };
+int pbr_rasterize_flags(pbr_context* ctx, const pbr_draw* draws, int32_t n_draws, const pbr_raster_view* view,
+                        const pbr_raster_targets* targets, uint32_t flags, void* stream);
+
+typedef struct pbr_raster_clip_stats {
+    int64_t clipped_near; /* source triangles with 1 or 2 vertices in front of z = 0 */
+    int64_t clip_pieces;  /* triangles emitted for them (1 or 2 each) */
+} pbr_raster_clip_stats;
+
+/* The clipping counters of the last rasterisation on `stream` (synchronises it, like pbr_last_raster_stats); zeros
+ * after an unflagged call and when the context has not rasterised on that stream. */
+int pbr_last_raster_clip_stats(pbr_context* ctx, pbr_raster_clip_stats* out, void* stream);
 
 /* ---- Host G-buffer fill (replaces the VS + rasteriser front-end, Default.hlsl:22-45) ---------- */
 

@@ -383,8 +383,10 @@ class ShadingContext {
     // VS + the rasteriser (Default.hlsl:22-45, DrawIndexedInstanced): `draws` in order under `view`
     // into rows [view.row_begin, view.row_end) of `attrs` (a full-frame buffer), with an optional depth plane of
     // attrs' row stride holding the same rows.
+    // `flags`: 0 (pbr_rasterize) or PBR_RASTER_CLIP_NEAR (pbr_rasterize_flags: triangles are clipped against the near
+    // plane, not skipped).
     void Rasterize(const std::vector<pbr_draw>& draws, const pbr_raster_view& view, DeviceAttributes& attrs,
-                   float* depth = nullptr, hipStream_t stream = nullptr) {
+                   float* depth = nullptr, hipStream_t stream = nullptr, uint32_t flags = 0) {
         const pbr_attributes_soa band = attrs.Band(view.row_begin, view.row_end);
         pbr_raster_targets t;
         std::memset(&t, 0, sizeof t);
@@ -399,7 +401,16 @@ class ShadingContext {
         t.material = const_cast<uint16_t*>(band.material);
         t.depth = depth;
         t.row_stride = band.row_stride;
-        Check(pbr_rasterize(ctx_, draws.data(), static_cast<int32_t>(draws.size()), &view, &t, stream), "pbr_rasterize");
+        if (flags == 0)
+            Check(pbr_rasterize(ctx_, draws.data(), static_cast<int32_t>(draws.size()), &view, &t, stream), "pbr_rasterize");
+        else
+            Check(pbr_rasterize_flags(ctx_, draws.data(), static_cast<int32_t>(draws.size()), &view, &t, flags, stream),
+                  "pbr_rasterize_flags");
+    }
+    pbr_raster_clip_stats LastRasterClipStats(hipStream_t stream = nullptr) {
+        pbr_raster_clip_stats s;
+        Check(pbr_last_raster_clip_stats(ctx_, &s, stream), "pbr_last_raster_clip_stats");
+        return s;
     }
     pbr_raster_stats LastRasterStats(hipStream_t stream = nullptr) {
         pbr_raster_stats s;

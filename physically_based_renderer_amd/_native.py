@@ -249,6 +249,16 @@ class RasterStats(ctypes.Structure):
     ]
 
 
+PBR_RASTER_CLIP_NEAR = 1 << 0
+
+
+class RasterClipStats(ctypes.Structure):
+    _fields_ = [
+        ("clipped_near", ctypes.c_int64),
+        ("clip_pieces", ctypes.c_int64),
+    ]
+
+
 class PassStats(ctypes.Structure):
     """pbr_pass_stats: statistics of the last shading pass."""
     _fields_ = [
@@ -304,6 +314,10 @@ SIGNATURES = {
     "pbr_rasterize": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(DrawDesc), ctypes.c_int32,
                                      ctypes.POINTER(RasterView), ctypes.POINTER(RasterTargets), ctypes.c_void_p]),
     "pbr_last_raster_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(RasterStats), ctypes.c_void_p]),
+    "pbr_rasterize_flags": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(DrawDesc), ctypes.c_int32,
+                                           ctypes.POINTER(RasterView), ctypes.POINTER(RasterTargets), ctypes.c_uint32,
+                                           ctypes.c_void_p]),
+    "pbr_last_raster_clip_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(RasterClipStats), ctypes.c_void_p]),
     "pbr_attributes_fill": (ctypes.c_int64, [ctypes.POINTER(SceneDesc), ctypes.c_int32, ctypes.c_int32,
                                              ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.c_int64,
                                              ctypes.c_int32]),

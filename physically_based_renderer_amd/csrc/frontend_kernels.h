@@ -59,18 +59,20 @@ struct RasterDraw {
     uint32_t pad[2];
 };
 // One transformed vertex of a draw: VS (Default.hlsl:27-42) and the viewport, DESIGN.md §12 steps 1-3.
-constexpr uint32_t kVertexNear = 1u, kVertexGuard = 2u;
+// kVertexOutside (written by a near-clipping call only, step 2a): PosH.z is not >= 0; such a vertex's X, Y, z and rw
+// are never read.
+constexpr uint32_t kVertexNear = 1u, kVertexGuard = 2u, kVertexOutside = 4u;
 struct RasterVertex {
     int32_t X, Y;    // window position in 1/256 pixel
     float z, rw;     // ndc.z and 1 / PosH.w
     float a[14];     // PosW, NormalW, TangentW, BitangentW, TexCoord
-    uint32_t flags;  // kVertexNear: w not > 0; kVertexGuard: beyond the guard band or not finite
+    uint32_t flags;  // kVertexNear: w not > 0; kVertexGuard: beyond the guard band or not finite; kVertexOutside
     uint32_t pad;
 };
-// Counters of a call, unsigned 64-bit words in device memory (pbr_raster_stats; kRasterLarge: the large-triangle
-// list's length).
+// Counters of a call, unsigned 64-bit words in device memory (pbr_raster_stats, pbr_raster_clip_stats; kRasterLarge:
+// the large-triangle list's length).
 enum RasterCounter { kRasterLarge = 0, kRasterCulled, kRasterZeroArea, kRasterNear, kRasterGuard, kRasterFragments,
-                     kRasterCounters = 8 };
+                     kRasterClipped, kRasterClipPieces, kRasterCounters = 8 };
 
 struct RasterArgs {
     const float* vertices;    // the mesh set: 14 floats per vertex
@@ -83,7 +85,7 @@ struct RasterArgs {
     uint32_t n_tris, n_records;
     RasterVertex* records;
     unsigned long long* vis;       // (row_end - row_begin) * width visibility words
-    uint2* large;                  // n_tris slots: (triangle, its 64 x 4 block count)
+    uint2* large;                  // n_large slots: (triangle, its 64 x 4 block count | piece << 31)
     unsigned long long* counters;  // kRasterCounters
     float view_proj[16];
     int width, height, row_begin, row_end;
@@ -93,9 +95,14 @@ struct RasterArgs {
     float* depth;  // or nullptr
     int64_t stride;
     bool vec;  // every plane 8-byte aligned, ids 4-byte, an even stride: paired stores
+    // Appended for pbr_rasterize_flags, so that the fields above keep their kernel-argument offsets.
+    bool clip_near;    // PBR_RASTER_CLIP_NEAR: the launches below start the kernels' clipping instantiations
+    float4* posh;      // clip_near: PosH of every vertex record (n_records); else nullptr
+    int64_t n_large;   // slots of `large`: n_tris, 2 n_tris when clip_near (a clipped triangle has up to two pieces)
 };
 // The stages of pbr_rasterize, each one launch (none when it has nothing to do): the vertex transform, the triangle
-// setup with the small triangles' coverage, the large triangles' coverage, the per-pixel resolve.
+// setup with the small triangles' coverage, the large triangles' coverage, the per-pixel resolve. With a.clip_near
+// each launches its near-clipping instantiation.
 hipError_t launch_raster_vertices(const RasterArgs& a, hipStream_t stream);
 hipError_t launch_raster_setup(const RasterArgs& a, hipStream_t stream);
 hipError_t launch_raster_large(const RasterArgs& a, hipStream_t stream);

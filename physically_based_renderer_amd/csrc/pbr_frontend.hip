@@ -226,11 +226,14 @@ int pbr_set_meshes(pbr_context* ctx, const pbr_mesh_desc* meshes, int32_t n_mesh
 
 namespace {
 
-// pbr_rasterize. `marks` (development, pbr_debug_rasterize_timed): six events recorded around the five stages --
-// clears and table upload, vertex transform, setup with the small triangles' coverage, large triangles, resolve.
+// pbr_rasterize (flags 0) and pbr_rasterize_flags. `marks` (development, pbr_debug_rasterize_timed): six events
+// recorded around the five stages -- clears and table upload, vertex transform, setup with the small triangles'
+// coverage, large triangles, resolve.
 int rasterize_impl(pbr_context* ctx, const pbr_draw* draws, int32_t n_draws, const pbr_raster_view* view,
-                   const pbr_raster_targets* tg, void* stream, hipEvent_t* marks) {
+                   const pbr_raster_targets* tg, uint32_t flags, void* stream, hipEvent_t* marks) {
     if (!ctx || !view || !tg || n_draws < 0 || (n_draws > 0 && !draws)) return PBR_ERR_INVALID_ARGUMENT;
+    if (flags & ~(uint32_t)PBR_RASTER_CLIP_NEAR) return PBR_ERR_INVALID_ARGUMENT;
+    const bool clip_near = (flags & PBR_RASTER_CLIP_NEAR) != 0;
     if (view->width < 0 || view->height < 0 || view->width > kRasterMaxSide || view->height > kRasterMaxSide)
         return PBR_ERR_INVALID_ARGUMENT;
     if (view->row_begin < 0 || view->row_begin > view->row_end || view->row_end > view->height)
@@ -272,6 +275,8 @@ int rasterize_impl(pbr_context* ctx, const pbr_draw* draws, int32_t n_draws, con
         n_records += mp.n_vertices;
     }
     if (n_tris > 0xFFFFFFFEull || n_records > 0x7FFFFFFFull) return PBR_ERR_INVALID_ARGUMENT;
+    // A clipped triangle lists up to two pieces: the list's length stays inside 32 bits.
+    if (clip_near && n_tris > 0x7FFFFFFFull) return PBR_ERR_INVALID_ARGUMENT;
     const int band_h = view->row_end - view->row_begin;
     if (view->width == 0 || band_h == 0) return PBR_OK;  // an empty band: nothing is read or written
 
@@ -312,13 +317,17 @@ int rasterize_impl(pbr_context* ctx, const pbr_draw* draws, int32_t n_draws, con
     h_tri[nd] = tri;
     h_rec[nd] = rec;
 
-    // Device scratch of this stream: counters | draw table | vertex records | large list | visibility words.
+    // Device scratch of this stream: counters | draw table | vertex records | large list | visibility words, and for
+    // a near-clipping call | PosH of every record, with a large list of two slots per triangle (16 bytes per record
+    // and 8 per triangle more).
+    const size_t n_large = (size_t)n_tris * (clip_near ? 2u : 1u);
     const size_t off_table = 256;
     const size_t off_records = off_table + align_up(table_bytes, 256);
     const size_t off_large = off_records + align_up(sizeof(pbr::RasterVertex) * (size_t)n_records, 256);
-    const size_t off_vis = off_large + align_up(sizeof(uint2) * (size_t)n_tris, 256);
+    const size_t off_vis = off_large + align_up(sizeof(uint2) * n_large, 256);
     const size_t vis_bytes = sizeof(unsigned long long) * (size_t)band_h * (size_t)view->width;
-    const size_t need = off_vis + vis_bytes;
+    const size_t off_posh = off_vis + align_up(vis_bytes, 256);
+    const size_t need = clip_near ? off_posh + sizeof(float4) * (size_t)n_records : off_vis + vis_bytes;
     if (need > rs.capacity) {  // grown in stream order: the stream's earlier rasterisations finish with the old block
         if (rs.d) {
             e = hipFreeAsync(rs.d, s);
@@ -338,6 +347,9 @@ int rasterize_impl(pbr_context* ctx, const pbr_draw* draws, int32_t n_draws, con
     a.records = reinterpret_cast<pbr::RasterVertex*>(rs.d + off_records);
     a.large = reinterpret_cast<uint2*>(rs.d + off_large);
     a.vis = reinterpret_cast<unsigned long long*>(rs.d + off_vis);
+    a.clip_near = clip_near;
+    a.posh = clip_near ? reinterpret_cast<float4*>(rs.d + off_posh) : nullptr;
+    a.n_large = (int64_t)n_large;
     a.n_draws = n_draws;
     a.n_tris = (uint32_t)n_tris;
     a.n_records = (uint32_t)n_records;
@@ -383,23 +395,47 @@ extern "C" {
 
 int pbr_rasterize(pbr_context* ctx, const pbr_draw* draws, int32_t n_draws, const pbr_raster_view* view,
                   const pbr_raster_targets* targets, void* stream) {
-    return rasterize_impl(ctx, draws, n_draws, view, targets, stream, nullptr);
+    return rasterize_impl(ctx, draws, n_draws, view, targets, 0u, stream, nullptr);
 }
 
-int pbr_last_raster_stats(pbr_context* ctx, pbr_raster_stats* out, void* stream) {
-    if (!ctx || !out) return PBR_ERR_INVALID_ARGUMENT;
-    *out = pbr_raster_stats{};
+int pbr_rasterize_flags(pbr_context* ctx, const pbr_draw* draws, int32_t n_draws, const pbr_raster_view* view,
+                        const pbr_raster_targets* targets, uint32_t flags, void* stream) {
+    return rasterize_impl(ctx, draws, n_draws, view, targets, flags, stream, nullptr);
+}
+
+}  // extern "C"
+
+// The counters of the last rasterisation on `stream` into h (synchronises it) and its triangle count; *ran false (and
+// nothing read) when the context has not rasterised on that stream.
+static int read_raster_counters(pbr_context* ctx, void* stream, unsigned long long h[pbr::kRasterCounters],
+                                int64_t* triangles, bool* ran, const char* what) {
+    *ran = false;
     Entry en(ctx);
     if (const int rc = en.device(stream)) return rc;
     const StreamState* st = nullptr;
     for (const StreamState& c : ctx->streams)
         if (c.stream == en.s && c.raster.ran) st = &c;
     if (!st) return PBR_OK;
-    unsigned long long h[pbr::kRasterCounters] = {};
-    hipError_t e = hipMemcpyAsync(h, st->raster.d_counters, sizeof(h), hipMemcpyDeviceToHost, en.s);
+    hipError_t e = hipMemcpyAsync(h, st->raster.d_counters, sizeof(unsigned long long) * pbr::kRasterCounters,
+                                  hipMemcpyDeviceToHost, en.s);
     if (e == hipSuccess) e = hipStreamSynchronize(en.s);
-    if (e != hipSuccess) return fail_hip(ctx, e, "pbr_last_raster_stats");
-    out->triangles = st->raster.triangles;
+    if (e != hipSuccess) return fail_hip(ctx, e, what);
+    *triangles = st->raster.triangles;
+    *ran = true;
+    return PBR_OK;
+}
+
+extern "C" {
+
+int pbr_last_raster_stats(pbr_context* ctx, pbr_raster_stats* out, void* stream) {
+    if (!ctx || !out) return PBR_ERR_INVALID_ARGUMENT;
+    *out = pbr_raster_stats{};
+    unsigned long long h[pbr::kRasterCounters] = {};
+    int64_t triangles = 0;
+    bool ran = false;
+    if (const int rc = read_raster_counters(ctx, stream, h, &triangles, &ran, "pbr_last_raster_stats")) return rc;
+    if (!ran) return PBR_OK;
+    out->triangles = triangles;
     out->backface_culled = (int64_t)h[pbr::kRasterCulled];
     out->zero_area = (int64_t)h[pbr::kRasterZeroArea];
     out->skipped_near = (int64_t)h[pbr::kRasterNear];
@@ -408,21 +444,33 @@ int pbr_last_raster_stats(pbr_context* ctx, pbr_raster_stats* out, void* stream)
     return PBR_OK;
 }
 
+int pbr_last_raster_clip_stats(pbr_context* ctx, pbr_raster_clip_stats* out, void* stream) {
+    if (!ctx || !out) return PBR_ERR_INVALID_ARGUMENT;
+    *out = pbr_raster_clip_stats{};
+    unsigned long long h[pbr::kRasterCounters] = {};  // every call clears them: zeros after an unflagged one
+    int64_t triangles = 0;
+    bool ran = false;
+    if (const int rc = read_raster_counters(ctx, stream, h, &triangles, &ran, "pbr_last_raster_clip_stats")) return rc;
+    out->clipped_near = (int64_t)h[pbr::kRasterClipped];
+    out->clip_pieces = (int64_t)h[pbr::kRasterClipPieces];
+    return PBR_OK;
+}
+
 }  // extern "C"
 
-// Development (tools/raster_bench.py; not in the public header): one pbr_rasterize with HIP events between its stages;
-// synchronises `stream` and writes the milliseconds of the clears and table upload, the vertex transform, the setup
-// with the small triangles' coverage, the large triangles' coverage and the per-pixel resolve into ms5.
-extern "C" int pbr_debug_rasterize_timed(pbr_context* ctx, const pbr_draw* draws, int32_t n_draws,
-                                         const pbr_raster_view* view, const pbr_raster_targets* targets, void* stream,
-                                         float* ms5) {
+// Development (tools/raster_bench.py; not in the public header): one pbr_rasterize_flags with HIP events between its
+// stages; synchronises `stream` and writes the milliseconds of the clears and table upload, the vertex transform, the
+// setup with the small triangles' coverage, the large triangles' coverage and the per-pixel resolve into ms5.
+extern "C" int pbr_debug_rasterize_flags_timed(pbr_context* ctx, const pbr_draw* draws, int32_t n_draws,
+                                               const pbr_raster_view* view, const pbr_raster_targets* targets,
+                                               uint32_t flags, void* stream, float* ms5) {
     if (!ctx || !ms5) return PBR_ERR_INVALID_ARGUMENT;
     DeviceGuard g(ctx->device);
     if (!g.ok) return PBR_ERR_NO_DEVICE;
     hipEvent_t ev[6] = {};
     hipError_t e = hipSuccess;
     for (int i = 0; i < 6 && e == hipSuccess; ++i) e = hipEventCreate(&ev[i]);
-    int rc = e == hipSuccess ? rasterize_impl(ctx, draws, n_draws, view, targets, stream, ev) : PBR_ERR_HIP;
+    int rc = e == hipSuccess ? rasterize_impl(ctx, draws, n_draws, view, targets, flags, stream, ev) : PBR_ERR_HIP;
     if (rc == PBR_OK && hipStreamSynchronize(static_cast<hipStream_t>(stream)) != hipSuccess) rc = PBR_ERR_HIP;
     for (int i = 0; i < 5; ++i) {
         ms5[i] = 0.0f;
@@ -431,4 +479,11 @@ extern "C" int pbr_debug_rasterize_timed(pbr_context* ctx, const pbr_draw* draws
     for (hipEvent_t x : ev)
         if (x) (void)hipEventDestroy(x);
     return rc;
+}
+
+// The same for pbr_rasterize.
+extern "C" int pbr_debug_rasterize_timed(pbr_context* ctx, const pbr_draw* draws, int32_t n_draws,
+                                         const pbr_raster_view* view, const pbr_raster_targets* targets, void* stream,
+                                         float* ms5) {
+    return pbr_debug_rasterize_flags_timed(ctx, draws, n_draws, view, targets, 0u, stream, ms5);
 }

@@ -18,6 +18,17 @@
 //      recomputed with the operations of the coverage test, the attributes interpolated and stored.
 // Visibility is one 64-bit word per band pixel, (bits(z) << 32) | triangle ordinal, cleared to all ones and lowered
 // by a global 64-bit atomicMin: the smallest key wins whatever the execution order.
+//
+// Near-plane clipping (pbr_rasterize_flags with PBR_RASTER_CLIP_NEAR) is a second instantiation
+// of each kernel (template parameter CLIP; raster_setup_clip_kernel for the setup, whose piece loop has another shape),
+// launched for a flagged call only; the CLIP = false instantiations are the kernels of pbr_rasterize, instruction for
+// instruction. The vertex kernel also stores PosH (16 bytes per record) and marks the vertices with PosH.z not >= 0
+// as outside. A triangle with 1 or 2 inside vertices becomes 1 or 2 pieces whose new vertices -- the crossings of its
+// edges with z = 0, each computed from the inside vertex to the outside one -- are never stored: setup, the
+// large-triangle kernel and the resolve rebuild a piece from the triangle's ordinal and the piece's number with the
+// same operations (piece_setup), so the resolve reproduces the key's z bits as it does for an unclipped triangle. A
+// large-list entry carries the piece's number in the top bit of its block count (a block count is below 2^23: frames
+// are at most 32,768 on a side).
 #pragma once
 
 #include "pbr_device_math.h"
@@ -54,7 +65,32 @@ __device__ __forceinline__ int find_draw(const uint32_t* prefix, int n, uint32_t
     return lo;
 }
 
-enum TriStatus { kTriDraw = 0, kTriNear, kTriGuard, kTriZeroArea, kTriCulled };
+// Steps 2-3 on a piece's new vertex (piece_setup): the near test on w, the three divisions, the viewport, the snap to
+// 1/256 pixel and the guard band, operation for operation what raster_vertex_kernel does to a submitted vertex (which
+// keeps them written out: calling this from it changes the unflagged kernel's register allocation and schedule).
+struct Projected {
+    int X, Y;
+    float z, rw;
+    uint32_t flags;  // kVertexNear | kVertexGuard
+};
+__device__ __forceinline__ Projected project(const RasterArgs& a, float x, float y, float z, float w) {
+    Projected o;
+    uint32_t flags = w > 0.0f ? 0u : kVertexNear;  // NaN: near
+    const float nx = x / w, ny = y / w, nz = z / w;
+    const float xs = (nx * 0.5f + 0.5f) * (float)a.width, ys = (0.5f - ny * 0.5f) * (float)a.height;
+    const float tx = xs * 256.0f, ty = ys * 256.0f;
+    const bool inside = fabsf(tx) < 0x1p23f && fabsf(ty) < 0x1p23f;  // false for NaN and inf
+    if (!inside) flags |= kVertexGuard;
+    o.X = inside ? (int)rintf(tx) : 0;
+    o.Y = inside ? (int)rintf(ty) : 0;
+    o.z = nz;
+    o.rw = 1.0f / w;
+    o.flags = flags;
+    return o;
+}
+
+// kTriClipped (CLIP only): 1 or 2 vertices are outside: the triangle is drawn as its pieces. kTriNone: no triangle.
+enum TriStatus { kTriDraw = 0, kTriNear, kTriGuard, kTriZeroArea, kTriCulled, kTriClipped, kTriNone };
 
 // A triangle after setup: its vertices' records and snapped positions in the order every
 // later step uses (1 and 2 exchanged for a back face drawn under cull none), the positive area, the draw.
@@ -65,13 +101,18 @@ struct Tri {
     int draw;
 };
 
-__device__ __forceinline__ TriStatus tri_setup(const RasterArgs& a, uint32_t t, Tri& s) {
+// CLIP: `outside` receives the mask of the vertices (in index order) marked kVertexOutside; with none of them the
+// triangle is set up as without CLIP, with all three it is kTriNear (step 2a: n = 0), otherwise kTriClipped with
+// s.rec in index order and s.draw set (piece_setup goes on from there).
+template <bool CLIP = false>
+__device__ __forceinline__ TriStatus tri_setup(const RasterArgs& a, uint32_t t, Tri& s, uint32_t* outside = nullptr) {
     const int d = find_draw(a.tri_prefix, a.n_draws, t);
     s.draw = d;
     const RasterDraw& dr = a.draws[PBR_BOUNDS((int64_t)d, (int64_t)a.n_draws, kBoundsRaster)];
     const uint32_t k = t - a.tri_prefix[PBR_BOUNDS((int64_t)d, (int64_t)a.n_draws + 1, kBoundsRaster)];
     const int64_t i0 = (int64_t)dr.idx_src + 3 * (int64_t)k;
     uint32_t flags = 0;
+    [[maybe_unused]] uint32_t mask = 0;
 #pragma unroll
     for (int v = 0; v < 3; ++v) {
         const uint32_t idx = a.indices[PBR_BOUNDS(i0 + v, a.n_src_indices, kBoundsMesh)];
@@ -80,6 +121,12 @@ __device__ __forceinline__ TriStatus tri_setup(const RasterArgs& a, uint32_t t, 
         s.X[v] = r.X;
         s.Y[v] = r.Y;
         flags |= r.flags;
+        if constexpr (CLIP) mask |= ((r.flags / kVertexOutside) & 1u) << v;
+    }
+    if constexpr (CLIP) {
+        *outside = mask;
+        if (mask == 7u) return kTriNear;
+        if (mask != 0u) return kTriClipped;
     }
     if (flags & kVertexNear) return kTriNear;
     if (flags & kVertexGuard) return kTriGuard;
@@ -172,6 +219,93 @@ __device__ __forceinline__ void load_z(const RasterArgs& a, const Tri& s, float 
     for (int v = 0; v < 3; ++v) z[v] = a.records[PBR_BOUNDS((int64_t)s.rec[v], (int64_t)a.n_records, kBoundsRaster)].z;
 }
 
+// ---- Near-plane clipping (step 2a) ----
+// A piece of a clipped triangle after setup: s as for a triangle, with s.rec[v] the submitted vertex that piece
+// vertex v is (recb[v] == s.rec[v]) or the inside end of the edge whose crossing with z = 0 it is (recb[v]: the outside
+// end); t, ndc z and 1 / w of the three vertices, in s's order.
+struct Piece {
+    Tri s;
+    uint32_t recb[3];
+    float t[3], z[3], rw[3];
+};
+
+__device__ __forceinline__ uint32_t pick3(const uint32_t r[3], int i) { return i == 0 ? r[0] : (i == 1 ? r[1] : r[2]); }
+
+// Pieces of a triangle with n inside vertices: 0, 1, 2 (and the triangle itself for 3).
+__device__ __forceinline__ int clip_pieces(uint32_t outside) {
+    const int n = 3 - (int)__popc(outside);
+    return n < 2 ? n : (n == 2 ? 2 : 1);
+}
+
+// Piece `piece` of the triangle `src` that tri_setup<true> returned kTriClipped for, with `outside` its mask: the
+// vertices of rule 2a.4, steps 2-3 on the new ones, then step 4 on the piece. With i the inside vertex of n = 1 or the
+// outside vertex of n = 2 and (i, j, k) in cyclic index order: n = 1: (v_i, c_ij, c_ik); n = 2: piece 0 (c_ji, v_j, v_k),
+// piece 1 (c_ji, v_k, c_ki), c_ab the crossing computed from inside a to outside b.
+__device__ __forceinline__ TriStatus piece_setup(const RasterArgs& a, const Tri& src, uint32_t outside, int piece,
+                                                 Piece& P) {
+    const bool one_inside = __popc(outside) == 2;
+    const uint32_t odd = one_inside ? (~outside & 7u) : outside;  // one bit
+    const int i = odd == 1u ? 0 : (odd == 2u ? 1 : 2);
+    const uint32_t ri = pick3(src.rec, i), rj = pick3(src.rec, (i + 1) % 3), rk = pick3(src.rec, (i + 2) % 3);
+    Tri& s = P.s;
+    if (one_inside) {
+        s.rec[0] = ri, s.rec[1] = ri, s.rec[2] = ri;
+        P.recb[0] = ri, P.recb[1] = rj, P.recb[2] = rk;
+    } else if (piece == 0) {
+        s.rec[0] = rj, s.rec[1] = rj, s.rec[2] = rk;
+        P.recb[0] = ri, P.recb[1] = rj, P.recb[2] = rk;
+    } else {
+        s.rec[0] = rj, s.rec[1] = rk, s.rec[2] = rk;
+        P.recb[0] = ri, P.recb[1] = rk, P.recb[2] = ri;
+    }
+    s.draw = src.draw;
+    uint32_t flags = 0;
+#pragma unroll
+    for (int v = 0; v < 3; ++v) {
+        if (P.recb[v] == s.rec[v]) {  // a submitted, inside vertex: its record
+            const RasterVertex& r = a.records[PBR_BOUNDS((int64_t)s.rec[v], (int64_t)a.n_records, kBoundsRaster)];
+            s.X[v] = r.X;
+            s.Y[v] = r.Y;
+            P.z[v] = r.z;
+            P.rw[v] = r.rw;
+            P.t[v] = 0.0f;
+            flags |= r.flags;
+        } else {  // the crossing, from the inside vertex to the outside one
+            const float4 pa = a.posh[PBR_BOUNDS((int64_t)s.rec[v], (int64_t)a.n_records, kBoundsRaster)];
+            const float4 pb = a.posh[PBR_BOUNDS((int64_t)P.recb[v], (int64_t)a.n_records, kBoundsRaster)];
+            const float t = pa.z / (pa.z - pb.z);
+            const Projected c = project(a, pa.x + t * (pb.x - pa.x), pa.y + t * (pb.y - pa.y), 0.0f,
+                                        pa.w + t * (pb.w - pa.w));
+            s.X[v] = c.X;
+            s.Y[v] = c.Y;
+            P.z[v] = c.z;
+            P.rw[v] = c.rw;
+            P.t[v] = t;
+            flags |= c.flags;
+        }
+    }
+    if (flags & kVertexNear) return kTriNear;
+    if (flags & kVertexGuard) return kTriGuard;
+    long long A = (long long)(s.X[1] - s.X[0]) * (long long)(s.Y[2] - s.Y[0]) -
+                  (long long)(s.X[2] - s.X[0]) * (long long)(s.Y[1] - s.Y[0]);
+    if (A == 0) return kTriZeroArea;
+    if (A < 0) {
+        if (a.draws[PBR_BOUNDS((int64_t)s.draw, (int64_t)a.n_draws, kBoundsRaster)].cull == 0u) return kTriCulled;
+        const uint32_t r1 = s.rec[1], b1 = P.recb[1];
+        s.rec[1] = s.rec[2], P.recb[1] = P.recb[2];
+        s.rec[2] = r1, P.recb[2] = b1;
+        const int x1 = s.X[1], y1 = s.Y[1];
+        s.X[1] = s.X[2], s.Y[1] = s.Y[2];
+        s.X[2] = x1, s.Y[2] = y1;
+        const float t1 = P.t[1], z1 = P.z[1], w1 = P.rw[1];
+        P.t[1] = P.t[2], P.z[1] = P.z[2], P.rw[1] = P.rw[2];
+        P.t[2] = t1, P.z[2] = z1, P.rw[2] = w1;
+        A = -A;
+    }
+    s.A = A;
+    return kTriDraw;
+}
+
 // Sum over the wave, then one atomic from its first lane. Every lane of the wave calls it.
 __device__ __forceinline__ void count_wave(unsigned long long* counter, uint32_t mine) {
     unsigned long long v = mine;
@@ -187,6 +321,8 @@ __device__ __forceinline__ void count_ballot(unsigned long long* counter, bool m
 }  // namespace raster
 
 // Stage 1: VS (Default.hlsl:27-42), the perspective division, the viewport and the snap.
+// CLIP: PosH is kept as well, and a vertex with PosH.z not >= 0 (NaN included; -0.0f is inside) is marked outside.
+template <bool CLIP>
 __global__ __launch_bounds__(256) void raster_vertex_kernel(const RasterArgs a) {
     using namespace raster;
     const uint32_t g = blockIdx.x * 256u + threadIdx.x;
@@ -213,7 +349,7 @@ __global__ __launch_bounds__(256) void raster_vertex_kernel(const RasterArgs a) 
     o.a[12] = mul4(tc[0], tc[1], tc[2], tc[3], dr.mat, 0);
     o.a[13] = mul4(tc[0], tc[1], tc[2], tc[3], dr.mat, 1);
 
-    const float w = ph[3];
+    const float w = ph[3];  // steps 2-3 (project() holds the same operations for a piece's new vertex)
     uint32_t flags = w > 0.0f ? 0u : kVertexNear;  // NaN: near
     const float nx = ph[0] / w, ny = ph[1] / w, nz = ph[2] / w;
     const float xs = (nx * 0.5f + 0.5f) * (float)a.width, ys = (0.5f - ny * 0.5f) * (float)a.height;
@@ -225,9 +361,49 @@ __global__ __launch_bounds__(256) void raster_vertex_kernel(const RasterArgs a) 
     o.z = nz;
     o.rw = 1.0f / w;
     o.flags = flags;
+    if constexpr (CLIP) {
+        if (!(ph[2] >= 0.0f)) o.flags |= kVertexOutside;
+        a.posh[PBR_BOUNDS((int64_t)g, (int64_t)a.n_records, kBoundsRaster)] = make_float4(ph[0], ph[1], ph[2], ph[3]);
+    }
     o.pad = 0u;
     a.records[PBR_BOUNDS((int64_t)g, (int64_t)a.n_records, kBoundsRaster)] = o;
 }
+
+namespace raster {
+
+// The two halves of raster_setup_kernel's tail as functions, for raster_setup_clip_kernel's piece loop (the unflagged
+// kernel keeps them written out: its code object is the one pbr_rasterize was measured with).
+// The coverage of a triangle (or piece) with a small box, by its setup lane; the fragments.
+__device__ __forceinline__ uint32_t raster_small(const RasterArgs& a, const Tri& s, const Box& b, const float z[3],
+                                                 uint32_t prim) {
+    Edges e;
+    tri_edges(s, e);
+    uint32_t frags = 0;
+    for (int y = b.y0; y <= b.y1; ++y)
+        for (int x = b.x0; x <= b.x1; ++x) frags += raster_pixel(a, s, e, z, prim, x, y);
+    return frags;
+}
+
+// Appends the wave's large triangles (or pieces: `piece` in the top bit of the block count) to the list: one atomic
+// per wave. Every lane of the wave calls it.
+__device__ __forceinline__ void append_large(const RasterArgs& a, bool large, const Box& b, uint32_t t, uint32_t piece,
+                                             int64_t slots) {
+    const uint64_t m = __ballot(large);
+    if (m != 0ull) {
+        const uint32_t lane = threadIdx.x & 63u;
+        const int leader = (int)__builtin_ctzll(m);
+        unsigned long long base = 0;
+        if ((int)lane == leader) base = atomicAdd(a.counters + kRasterLarge, (unsigned long long)__popcll(m));
+        base = __shfl(base, leader, 64);
+        if (large) {  // the triangle and its block count: a workgroup whose slab has no block of it skips it unread
+            const uint32_t rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+            const uint32_t nb = ((uint32_t)(b.x1 - b.x0) / kBlockW + 1u) * ((uint32_t)(b.y1 - b.y0) / kBlockH + 1u);
+            a.large[PBR_BOUNDS((int64_t)base + rank, slots, kBoundsRaster)] = make_uint2(t, nb | (piece << 31));
+        }
+    }
+}
+
+}  // namespace raster
 
 // Stage 2: setup of every triangle, the statistics, the small triangles' coverage, the large list.
 __global__ __launch_bounds__(256) void raster_setup_kernel(const RasterArgs a) {
@@ -273,27 +449,93 @@ __global__ __launch_bounds__(256) void raster_setup_kernel(const RasterArgs a) {
     }
 }
 
+// Stage 2 with near clipping: the lane of a clipped triangle walks its (at most two) pieces; each is counted,
+// rasterised or listed as a submitted triangle would be. Both rounds of the piece loop are taken by every lane, so the
+// wave-wide ballots and sums inside it see the whole wave.
+__global__ __launch_bounds__(256) void raster_setup_clip_kernel(const RasterArgs a) {
+    using namespace raster;
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    Tri src;
+    uint32_t outside = 0;
+    TriStatus st = kTriNone;
+    if (t < a.n_tris) st = tri_setup<true>(a, t, src, &outside);
+    const bool clipped = st == kTriClipped;
+    const int n_pieces = clipped ? clip_pieces(outside) : (st == kTriDraw ? 1 : 0);
+    count_ballot(a.counters + kRasterClipped, clipped);
+    count_wave(a.counters + kRasterClipPieces, clipped ? (uint32_t)n_pieces : 0u);
+    // what the triangle itself adds to the skip counters; its pieces add theirs below
+    uint32_t culled = st == kTriCulled, zero = st == kTriZeroArea, near = st == kTriNear, guard = st == kTriGuard;
+    uint32_t frags = 0;
+    for (int p = 0; p < 2; ++p) {
+        Piece P;
+        Box b{0, -1, 0, -1};
+        TriStatus ps = kTriNone;
+        if (p < n_pieces) {
+            if (clipped) {
+                ps = piece_setup(a, src, outside, p, P);
+                culled += ps == kTriCulled, zero += ps == kTriZeroArea, near += ps == kTriNear, guard += ps == kTriGuard;
+            } else {
+                P.s = src;
+                ps = kTriDraw;
+            }
+        }
+        const bool draw = ps == kTriDraw && tri_box(a, P.s, b);
+        const long long npix = draw ? (long long)(b.x1 - b.x0 + 1) * (long long)(b.y1 - b.y0 + 1) : 0;
+        const bool small = draw && npix <= kSmallPixels, large = draw && !small;
+        if (small) {
+            if (!clipped) load_z(a, P.s, P.z);
+            frags += raster_small(a, P.s, b, P.z, t);
+        }
+        append_large(a, large, b, t, (uint32_t)p, a.n_large);
+    }
+    count_wave(a.counters + kRasterCulled, culled);
+    count_wave(a.counters + kRasterZeroArea, zero);
+    count_wave(a.counters + kRasterNear, near);
+    count_wave(a.counters + kRasterGuard, guard);
+    count_wave(a.counters + kRasterFragments, frags);
+}
+
 // Stage 3: the large triangles. blockIdx.x strides over the list, blockIdx.y over the triangle's 64 x 4 blocks; a wave
-// is one row of a block. All control flow outside the pixel test is uniform over the workgroup.
+// is one row of a block. All control flow outside the pixel test is uniform over the workgroup. CLIP: an entry names a
+// triangle or, with the piece's number in the top bit of its block count, a piece of a clipped one.
+template <bool CLIP>
 __global__ __launch_bounds__(256) void raster_large_kernel(const RasterArgs a) {
     using namespace raster;
     const unsigned long long listed = a.counters[kRasterLarge];
-    const uint32_t n_large = listed < (unsigned long long)a.n_tris ? (uint32_t)listed : a.n_tris;
+    const uint32_t slots = CLIP ? (uint32_t)a.n_large : a.n_tris;
+    const uint32_t n_large = listed < (unsigned long long)slots ? (uint32_t)listed : slots;
     uint32_t frags = 0;
     for (uint32_t i = blockIdx.x; i < n_large; i += gridDim.x) {
-        const uint2 entry = a.large[PBR_BOUNDS((int64_t)i, (int64_t)a.n_tris, kBoundsRaster)];
-        if (blockIdx.y >= entry.y) continue;
+        const uint2 entry = a.large[PBR_BOUNDS((int64_t)i, (int64_t)slots, kBoundsRaster)];
+        const uint32_t blocks = CLIP ? entry.y & 0x7FFFFFFFu : entry.y;
+        if (blockIdx.y >= blocks) continue;
         const uint32_t t = entry.x;
         Tri s;
         Box b;
-        if (tri_setup(a, t, s) != kTriDraw || !tri_box(a, s, b)) continue;  // never: the setup kernel listed it
+        float z[3];
+        if constexpr (CLIP) {
+            uint32_t outside = 0;
+            const TriStatus st = tri_setup<true>(a, t, s, &outside);
+            if (st == kTriClipped) {
+                Piece P;
+                if (piece_setup(a, s, outside, (int)(entry.y >> 31), P) != kTriDraw) continue;  // never, as below
+                s = P.s;
+#pragma unroll
+                for (int v = 0; v < 3; ++v) z[v] = P.z[v];
+            } else {
+                if (st != kTriDraw) continue;
+                load_z(a, s, z);
+            }
+            if (!tri_box(a, s, b)) continue;
+        } else {
+            if (tri_setup(a, t, s) != kTriDraw || !tri_box(a, s, b)) continue;  // never: the setup kernel listed it
+        }
         const uint32_t nbx = (uint32_t)(b.x1 - b.x0) / kBlockW + 1u, nby = (uint32_t)(b.y1 - b.y0) / kBlockH + 1u;
         const uint32_t nb = nbx * nby;
         if (blockIdx.y >= nb) continue;
         Edges e;
         tri_edges(s, e);
-        float z[3];
-        load_z(a, s, z);
+        if constexpr (!CLIP) load_z(a, s, z);
         for (uint32_t blk = blockIdx.y; blk < nb; blk += gridDim.y) {
             const int X0 = b.x0 + (int)(blk % nbx) * kBlockW, Y0 = b.y0 + (int)(blk / nbx) * kBlockH;
             const int X1 = min(X0 + kBlockW - 1, b.x1), Y1 = min(Y0 + kBlockH - 1, b.y1);
@@ -314,30 +556,93 @@ __global__ __launch_bounds__(256) void raster_large_kernel(const RasterArgs a) {
 
 namespace raster {
 
+// Step 9: a pixel without a fragment.
+__device__ __forceinline__ void background_pixel(const RasterArgs& a, int x, int y, float out[14], uint32_t& material,
+                                                 float& depth) {
+    const float sx = (float)(2 * x + 1) / (float)a.width - 1.0f;
+    const float sy = 1.0f - (float)(2 * y + 1) / (float)a.height;
+    float d[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) d[c] = (a.fwd[c] + sx * a.right[c]) + sy * a.up[c];
+    const float len = sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float n = d[c] / len;
+        out[3 + c] = n;
+        out[c] = a.eye[c] + n * 100.0f;
+    }
+#pragma unroll
+    for (int k = 6; k < 14; ++k) out[k] = 0.0f;
+    material = 0xFFFFu;
+    depth = 1.0f;
+}
+
+// Step 2a.8: the winner is a clipped triangle: its lowest-numbered piece that covers the pixel centre with a z in
+// [0, 1) whose bits are the key's; the attributes from that piece's vertices, a new vertex's as a + t (b - a) from its
+// edge's inside end a to its outside end b. False when no piece qualifies (never: one of them wrote the key).
+__device__ __forceinline__ bool resolve_clipped(const RasterArgs& a, const Tri& src, uint32_t outside,
+                                                unsigned long long key, int x, int y, float out[14],
+                                                uint32_t& material, float& depth) {
+    const int n_pieces = clip_pieces(outside);
+    for (int piece = 0; piece < n_pieces; ++piece) {
+        Piece P;
+        if (piece_setup(a, src, outside, piece, P) != kTriDraw) continue;
+        Edges e;
+        tri_edges(P.s, e);
+        const long long E[3] = {edge_at(e, 0, x, y), edge_at(e, 1, x, y), edge_at(e, 2, x, y)};
+        if (!covered(e, E)) continue;
+        float l[3], p[3], q[3];
+        barycentrics(E, P.s.A, l);
+        const float zf = interpolate_z(l, P.z);
+        if (!(zf >= 0.0f && zf < 1.0f) || __float_as_uint(zf) != (uint32_t)(key >> 32)) continue;
+        depth = zf;
+#pragma unroll
+        for (int v = 0; v < 3; ++v) p[v] = l[v] * P.rw[v];
+        const float sum = (p[0] + p[1]) + p[2];
+#pragma unroll
+        for (int v = 0; v < 3; ++v) q[v] = p[v] / sum;
+        const RasterVertex *ra[3], *rb[3];
+#pragma unroll
+        for (int v = 0; v < 3; ++v) {
+            ra[v] = a.records + PBR_BOUNDS((int64_t)P.s.rec[v], (int64_t)a.n_records, kBoundsRaster);
+            rb[v] = a.records + PBR_BOUNDS((int64_t)P.recb[v], (int64_t)a.n_records, kBoundsRaster);
+        }
+#pragma unroll
+        for (int k = 0; k < 14; ++k) {
+            float av[3];
+#pragma unroll
+            for (int v = 0; v < 3; ++v) {
+                const float fa = ra[v]->a[k], fb = rb[v]->a[k];
+                av[v] = P.recb[v] == P.s.rec[v] ? fa : fa + P.t[v] * (fb - fa);
+            }
+            out[k] = (q[0] * av[0] + q[1] * av[1]) + q[2] * av[2];
+        }
+        material = a.draws[PBR_BOUNDS((int64_t)P.s.draw, (int64_t)a.n_draws, kBoundsRaster)].material;
+        return true;
+    }
+    return false;
+}
+
 // One pixel of the band: the winner's attributes (step 8) or the background (step 9).
+template <bool CLIP>
 __device__ __forceinline__ void resolve_pixel(const RasterArgs& a, int x, int y, float out[14], uint32_t& material,
                                               float& depth) {
     [[maybe_unused]] const int64_t n_vis = (int64_t)(a.row_end - a.row_begin) * a.width;
     const unsigned long long key = a.vis[PBR_BOUNDS((int64_t)(y - a.row_begin) * a.width + x, n_vis, kBoundsRaster)];
     Tri s;
-    if (key == ~0ull || tri_setup(a, (uint32_t)key, s) != kTriDraw) {  // (a winner always sets up as drawn)
-        const float sx = (float)(2 * x + 1) / (float)a.width - 1.0f;
-        const float sy = 1.0f - (float)(2 * y + 1) / (float)a.height;
-        float d[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) d[c] = (a.fwd[c] + sx * a.right[c]) + sy * a.up[c];
-        const float len = sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float n = d[c] / len;
-            out[3 + c] = n;
-            out[c] = a.eye[c] + n * 100.0f;
+    if constexpr (CLIP) {
+        uint32_t outside = 0;
+        const TriStatus st = key == ~0ull ? kTriNone : tri_setup<true>(a, (uint32_t)key, s, &outside);
+        if (st == kTriClipped && resolve_clipped(a, s, outside, key, x, y, out, material, depth)) return;
+        if (st != kTriDraw) {
+            background_pixel(a, x, y, out, material, depth);
+            return;
         }
-#pragma unroll
-        for (int k = 6; k < 14; ++k) out[k] = 0.0f;
-        material = 0xFFFFu;
-        depth = 1.0f;
-        return;
+    } else {
+        if (key == ~0ull || tri_setup(a, (uint32_t)key, s) != kTriDraw) {  // (a winner always sets up as drawn)
+            background_pixel(a, x, y, out, material, depth);
+            return;
+        }
     }
     Edges e;
     tri_edges(s, e);
@@ -363,7 +668,7 @@ __device__ __forceinline__ void resolve_pixel(const RasterArgs& a, int x, int y,
 
 // Stage 4: per pixel, the material resolve's tile: 256 threads over 64 x 8 pixels, a pixel pair per lane, 8-byte
 // plane stores when VEC.
-template <bool VEC>
+template <bool VEC, bool CLIP>
 __global__ __launch_bounds__(256) void raster_resolve_kernel(const RasterArgs a) {
     using namespace raster;
     const int band_h = a.row_end - a.row_begin;
@@ -372,8 +677,8 @@ __global__ __launch_bounds__(256) void raster_resolve_kernel(const RasterArgs a)
     const bool in0 = yb < band_h && x < a.width, in1 = yb < band_h && x + 1 < a.width;
     float v0[14], v1[14], z0 = 1.0f, z1 = 1.0f;
     uint32_t m0 = 0xFFFFu, m1 = 0xFFFFu;
-    if (in0) resolve_pixel(a, x, a.row_begin + yb, v0, m0, z0);
-    if (in1) resolve_pixel(a, x + 1, a.row_begin + yb, v1, m1, z1);
+    if (in0) resolve_pixel<CLIP>(a, x, a.row_begin + yb, v0, m0, z0);
+    if (in1) resolve_pixel<CLIP>(a, x + 1, a.row_begin + yb, v1, m1, z1);
     const int64_t oi = (int64_t)yb * a.stride + x;
     if (VEC && in1) {
         const int64_t i = PBR_BOUNDS_PIXEL(oi, a.width, band_h, a.stride, 2, kBoundsOutput);
@@ -401,21 +706,32 @@ __global__ __launch_bounds__(256) void raster_resolve_kernel(const RasterArgs a)
 
 hipError_t launch_raster_vertices(const RasterArgs& a, hipStream_t stream) {
     if (a.n_records == 0u) return hipSuccess;
-    hipLaunchKernelGGL(raster_vertex_kernel, dim3((a.n_records + 255u) / 256u), dim3(256), 0, stream, a);
+    const dim3 grid((a.n_records + 255u) / 256u);
+    if (a.clip_near)
+        hipLaunchKernelGGL((raster_vertex_kernel<true>), grid, dim3(256), 0, stream, a);
+    else
+        hipLaunchKernelGGL((raster_vertex_kernel<false>), grid, dim3(256), 0, stream, a);
     return hipGetLastError();
 }
 
 hipError_t launch_raster_setup(const RasterArgs& a, hipStream_t stream) {
     if (a.n_tris == 0u) return hipSuccess;
-    hipLaunchKernelGGL(raster_setup_kernel, dim3((uint32_t)(((uint64_t)a.n_tris + 255u) / 256u)), dim3(256), 0, stream,
-                       a);
+    const dim3 grid((uint32_t)(((uint64_t)a.n_tris + 255u) / 256u));
+    if (a.clip_near)
+        hipLaunchKernelGGL(raster_setup_clip_kernel, grid, dim3(256), 0, stream, a);
+    else
+        hipLaunchKernelGGL(raster_setup_kernel, grid, dim3(256), 0, stream, a);
     return hipGetLastError();
 }
 
 hipError_t launch_raster_large(const RasterArgs& a, hipStream_t stream) {
     if (a.n_tris == 0u) return hipSuccess;
     const uint32_t gx = a.n_tris < (uint32_t)raster::kLargeGridX ? a.n_tris : (uint32_t)raster::kLargeGridX;
-    hipLaunchKernelGGL(raster_large_kernel, dim3(gx, raster::kLargeSlabs), dim3(256), 0, stream, a);
+    const dim3 grid(gx, raster::kLargeSlabs);
+    if (a.clip_near)
+        hipLaunchKernelGGL((raster_large_kernel<true>), grid, dim3(256), 0, stream, a);
+    else
+        hipLaunchKernelGGL((raster_large_kernel<false>), grid, dim3(256), 0, stream, a);
     return hipGetLastError();
 }
 
@@ -423,10 +739,16 @@ hipError_t launch_raster_resolve(const RasterArgs& a, hipStream_t stream) {
     const int band_h = a.row_end - a.row_begin;
     if (a.width <= 0 || band_h <= 0) return hipSuccess;
     const dim3 grid((a.width + 63) / 64, (band_h + 7) / 8);
-    if (a.vec)
-        hipLaunchKernelGGL((raster_resolve_kernel<true>), grid, dim3(256), 0, stream, a);
-    else
-        hipLaunchKernelGGL((raster_resolve_kernel<false>), grid, dim3(256), 0, stream, a);
+    if (a.clip_near) {
+        if (a.vec)
+            hipLaunchKernelGGL((raster_resolve_kernel<true, true>), grid, dim3(256), 0, stream, a);
+        else
+            hipLaunchKernelGGL((raster_resolve_kernel<false, true>), grid, dim3(256), 0, stream, a);
+    } else if (a.vec) {
+        hipLaunchKernelGGL((raster_resolve_kernel<true, false>), grid, dim3(256), 0, stream, a);
+    } else {
+        hipLaunchKernelGGL((raster_resolve_kernel<false, false>), grid, dim3(256), 0, stream, a);
+    }
     return hipGetLastError();
 }
 

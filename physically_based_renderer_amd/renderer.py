@@ -444,11 +444,19 @@ class ShadingContext:
                 "pbr_set_meshes", self._h)
         self.meshes = meshes
 
-    def rasterize(self, draws: Sequence[Draw], view: View, out=None, stream=None) -> Attributes:
+    def rasterize(self, draws: Sequence[Draw], view: View, out=None, stream=None,
+                  clip_near: bool = False) -> Attributes:
         """VS and the rasteriser on the device (pbr_rasterize): ``draws`` in order under ``view`` into
         the attribute planes :meth:`resolve` consumes, asynchronously. ``out``: an ``Attributes`` holding the view's
         row band, or an ``(Attributes, depth)`` pair with an (H, row_stride) float32 depth plane; default: fresh
-        tensors. The result carries the depth plane as ``.depth`` (None when ``out`` had none)."""
+        tensors. The result carries the depth plane as ``.depth`` (None when ``out`` had none). ``clip_near``
+        (pbr_rasterize_flags with PBR_RASTER_CLIP_NEAR): triangles that cross the near plane are clipped against it
+        and drawn, not skipped (step 2a)."""
+        return self.rasterize_flags(draws, view, N.PBR_RASTER_CLIP_NEAR if clip_near else None, out=out, stream=stream)
+
+    def rasterize_flags(self, draws: Sequence[Draw], view: View, flags, out=None, stream=None) -> Attributes:
+        """:meth:`rasterize` through pbr_rasterize_flags with the given ``flags`` word (0: the same result as
+        pbr_rasterize; an unknown bit raises ``PbrError(PBR_ERR_INVALID_ARGUMENT)``); ``flags`` None: pbr_rasterize."""
         v = view.to_c()
         rows = v.row_end - v.row_begin
         dev = torch.device("cuda", self.device)
@@ -474,8 +482,13 @@ class ShadingContext:
         t.row_stride = int(attrs.row_stride)
         meshes = getattr(self, "meshes", ())
         c_draws = (N.DrawDesc * max(len(draws), 1))(*[d.to_c(meshes) for d in draws])
-        N.check(self.lib.pbr_rasterize(self._h, c_draws, len(draws), ctypes.byref(v), ctypes.byref(t),
-                                       ctypes.c_void_p(_stream_handle(stream))), "pbr_rasterize", self._h)
+        if flags is None:
+            N.check(self.lib.pbr_rasterize(self._h, c_draws, len(draws), ctypes.byref(v), ctypes.byref(t),
+                                           ctypes.c_void_p(_stream_handle(stream))), "pbr_rasterize", self._h)
+        else:
+            N.check(self.lib.pbr_rasterize_flags(self._h, c_draws, len(draws), ctypes.byref(v), ctypes.byref(t),
+                                                 int(flags), ctypes.c_void_p(_stream_handle(stream))),
+                    "pbr_rasterize_flags", self._h)
         attrs.depth = depth
         return attrs
 
@@ -486,6 +499,14 @@ class ShadingContext:
         N.check(self.lib.pbr_last_raster_stats(self._h, ctypes.byref(st), ctypes.c_void_p(_stream_handle(stream))),
                 "pbr_last_raster_stats", self._h)
         return {name: getattr(st, name) for name, _ in N.RasterStats._fields_}
+
+    def raster_clip_stats(self, stream=None) -> dict:
+        """pbr_last_raster_clip_stats of the last :meth:`rasterize` on ``stream`` (synchronises it): clipped_near,
+        clip_pieces; zeros after a call without ``clip_near``."""
+        st = N.RasterClipStats()
+        N.check(self.lib.pbr_last_raster_clip_stats(self._h, ctypes.byref(st), ctypes.c_void_p(_stream_handle(stream))),
+                "pbr_last_raster_clip_stats", self._h)
+        return {name: getattr(st, name) for name, _ in N.RasterClipStats._fields_}
 
     def _check_device(self, *tensors) -> None:
         """Every tensor handed to the kernel must live on this context's device: a foreign pointer would be

@@ -1,8 +1,11 @@
-"""Time the device rasteriser (pbr_rasterize) at 3840x2160 on two scenes, in one process on one GPU:
+"""Time the device rasteriser (pbr_rasterize) at 3840x2160 on three scenes, in one process on one GPU:
 
-  reference  the reference's 58 spheres as 64 x 32 UV spheres (3,968 triangles each, 230,144 in all) from the
-             overview camera;
-  stress     ~10^6 triangles of about a pixel, uniformly over the frame.
+  reference    the reference's 58 spheres as 64 x 32 UV spheres (3,968 triangles each, 230,144 in all) from the
+               overview camera;
+  stress       ~10^6 triangles of about a pixel, uniformly over the frame;
+  walkthrough  the reference scene over a floor of 64 x 64 quads, the eye one unit above the floor between the spheres
+               of the bottom row: spheres and floor cross the near plane. Only near-plane clipping
+               (pbr_rasterize_flags with PBR_RASTER_CLIP_NEAR) draws those triangles.
 
 Four legs per scene:
   (a) the stages of one call, HIP events between them (pbr_debug_rasterize_timed): clears and table upload, the
@@ -13,8 +16,13 @@ Four legs per scene:
       streaming yardstick;
   (d) reference scene only: the host route to the same planes, pbr_attributes_fill on 16 threads plus the upload
       (the analytic spheres, not the facets: DESIGN.md §12).
+Legs (a) and (b) are taken unflagged and then, when the library has pbr_rasterize_flags, with PBR_RASTER_CLIP_NEAR
+("clip": true in the line), with the clip counters of the call.
 
-    python tools/raster_bench.py [--width 3840 --height 2160] [--steps 50] [--log profiles/r10/raster_bench.log]
+    python tools/raster_bench.py [--width 3840 --height 2160] [--steps 50] [--log profiles/r11/raster_bench.log]
+
+--other-sources accepts a product build of another checkout (an A/B against the parent's library through
+PBR_LIB_PATH); the line records whose sources it was built from.
 """
 import argparse
 import ctypes
@@ -71,12 +79,39 @@ def stress_scene(W, H, n_tris, seed=7):
     return [Mesh(v.reshape(-1, 14), np.arange(3 * n_tris, dtype=np.uint32))], [Draw(cull=1)], view
 
 
-def timed_stages(ctx, draws, view, attrs, depth, steps):
+def walkthrough_scene(W, H, slices, stacks, quads=64):
+    """The reference scene's draws plus a floor of quads x quads quads at y = -16.5 (half a unit under the bottom row
+    of spheres), and a camera one unit above the floor between two spheres of that row, looking up the grid."""
+    meshes, draws = S.reference_scene_draws(slices, stacks)
+    j, i = np.meshgrid(np.arange(quads + 1), np.arange(quads + 1), indexing="ij")
+    v = np.zeros(((quads + 1) ** 2, 14), np.float32)
+    v[:, 0], v[:, 1], v[:, 2] = (-12.0 + 24.0 * i / quads).ravel(), -16.5, (-12.0 + 24.0 * j / quads).ravel()
+    v[:, 4], v[:, 6], v[:, 11] = 1.0, 1.0, 1.0
+    v[:, 12], v[:, 13] = (i / quads).ravel(), (j / quads).ravel()
+    ring = quads + 1
+    c, r = np.meshgrid(np.arange(quads), np.arange(quads))
+    v00 = (r * ring + c).ravel()
+    tris = np.stack([v00, v00 + ring, v00 + 1, v00 + 1, v00 + ring, v00 + ring + 1], -1)  # facing up
+    meshes = meshes + [Mesh(v, tris.astype(np.uint32).reshape(-1))]
+    draws = draws + [Draw(mesh=1, material=0)]
+    view = S.look_at_view((1.25, -15.5, -0.5), (-7.5, -14.5, 1.5), float(np.pi / 3), W, H)
+    return meshes, draws, view
+
+
+def timed_stages(ctx, draws, view, attrs, depth, steps, clip=False):
     """Per-stage medians of `steps` timed calls (each synchronises; the clock ramp is the untimed loop before)."""
-    fn = ctx.lib.pbr_debug_rasterize_timed
-    fn.restype = ctypes.c_int
-    fn.argtypes = [ctypes.c_void_p, ctypes.POINTER(N.DrawDesc), ctypes.c_int32, ctypes.POINTER(N.RasterView),
-                   ctypes.POINTER(N.RasterTargets), ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
+    argtypes = [ctypes.c_void_p, ctypes.POINTER(N.DrawDesc), ctypes.c_int32, ctypes.POINTER(N.RasterView),
+                ctypes.POINTER(N.RasterTargets), ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
+    if clip:
+        timed = ctx.lib.pbr_debug_rasterize_flags_timed
+        timed.argtypes = argtypes[:5] + [ctypes.c_uint32] + argtypes[5:]
+
+        def fn(h, c_draws, n, v, t, stream, ms):
+            return timed(h, c_draws, n, v, t, N.PBR_RASTER_CLIP_NEAR, stream, ms)
+    else:
+        timed = fn = ctx.lib.pbr_debug_rasterize_timed
+        timed.argtypes = argtypes
+    timed.restype = ctypes.c_int
     v = view.to_c()
     t = N.RasterTargets()
     ps = attrs.planes.stride(0) * 4
@@ -88,7 +123,7 @@ def timed_stages(ctx, draws, view, attrs, depth, steps):
     rows = []
     t0 = time.perf_counter()
     while time.perf_counter() - t0 < 0.2:  # clock ramp
-        ctx.rasterize(draws, view, out=(attrs, depth))
+        ctx.rasterize(draws, view, out=(attrs, depth), **({"clip_near": True} if clip else {}))
     for _ in range(steps):
         N.check(fn(ctx.handle, c_draws, len(draws), ctypes.byref(v), ctypes.byref(t), stream, ms),
                 "pbr_debug_rasterize_timed", ctx.handle)
@@ -106,10 +141,13 @@ def main():
     ap.add_argument("--slices", type=int, default=64)
     ap.add_argument("--stacks", type=int, default=32)
     ap.add_argument("--log", default=None, help="append the result lines to this file too")
+    ap.add_argument("--other-sources", action="store_true",
+                    help="accept a product build of another checkout's sources (A/B through PBR_LIB_PATH)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("raster_bench: no GPU visible (timings are taken on the device only)")
-    problems = N.build_problems()
+    info = N.build_info()
+    problems = N.build_problems(info, info["sources_sha"] if a.other_sources else None)
     if problems:
         sys.exit("raster_bench: not the product build of this checkout: " + "; ".join(problems))
     W, H = a.width, a.height
@@ -121,12 +159,16 @@ def main():
         print(line, flush=True)
         lines.append(line)
 
-    emit({"tool": "raster_bench", "width": W, "height": H, "sources_sha": N.build_info()["sources_sha"],
+    can_clip = hasattr(N.lib(), "pbr_rasterize_flags")
+    emit({"tool": "raster_bench", "width": W, "height": H, "sources_sha": info["sources_sha"],
+          "checkout_sha": N.kernel_sources_sha(), "library": os.path.relpath(info["path"], ROOT),
+          "has_rasterize_flags": can_clip,
           "device": torch.cuda.get_device_name(0), "steps": a.steps, "resolve_bytes_per_pixel": BYTES_WRITTEN})
     cfg = S.REFERENCE_SCENE.with_size(W, H).with_camera(*S.OVERVIEW_CAMERA)
     ref_meshes, ref_draws = S.reference_scene_draws(a.slices, a.stacks)
     scenes = [("reference", ref_meshes, ref_draws, S.reference_scene_view(cfg)),
-              ("stress",) + stress_scene(W, H, a.stress_triangles)]
+              ("stress",) + stress_scene(W, H, a.stress_triangles),
+              ("walkthrough",) + walkthrough_scene(W, H, a.slices, a.stacks)]
     attrs = Attributes(torch.empty((14, H, W), dtype=torch.float32, device=dev),
                        torch.empty((H, W), dtype=torch.int16, device=dev))
     depth = torch.empty((H, W), dtype=torch.float32, device=dev)
@@ -138,18 +180,22 @@ def main():
         emit(c)
         for name, meshes, draws, view in scenes:
             ctx.set_meshes(meshes)
-            ctx.rasterize(draws, view, out=(attrs, depth))
-            stats = ctx.raster_stats()
-            covered = int((attrs.material != -1).sum().item())
-            emit({"scene": name, "stats": stats, "covered_pixels": covered,
-                  "vertices": int(sum(m.vertices.shape[0] for m in meshes)), "draws": len(draws)})
-            st = timed_stages(ctx, draws, view, attrs, depth, a.steps)
-            st.update(leg="a_stages_ms", scene=name, coverage_ms=st["setup_small"] + st["large"],
-                      resolve_over_copy=st["resolve"] / c["median_ms"])
-            emit(st)
-            whole = event_ms(lambda: ctx.rasterize(draws, view, out=(attrs, depth)), a.steps)
-            whole.update(leg="b_whole_call", scene=name)
-            emit(whole)
+            for clip in (False, True) if can_clip else (False,):
+                kw = {"clip_near": True} if clip else {}
+                ctx.rasterize(draws, view, out=(attrs, depth), **kw)
+                stats = ctx.raster_stats()
+                if clip:
+                    stats.update(ctx.raster_clip_stats())
+                covered = int((attrs.material != -1).sum().item())
+                emit({"scene": name, "clip": clip, "stats": stats, "covered_pixels": covered,
+                      "vertices": int(sum(m.vertices.shape[0] for m in meshes)), "draws": len(draws)})
+                st = timed_stages(ctx, draws, view, attrs, depth, a.steps, clip)
+                st.update(leg="a_stages_ms", scene=name, clip=clip, coverage_ms=st["setup_small"] + st["large"],
+                          resolve_over_copy=st["resolve"] / c["median_ms"])
+                emit(st)
+                whole = event_ms(lambda: ctx.rasterize(draws, view, out=(attrs, depth), **kw), a.steps)
+                whole.update(leg="b_whole_call", scene=name, clip=clip)
+                emit(whole)
         host = []
         for _ in range(3):
             t0 = time.perf_counter()
