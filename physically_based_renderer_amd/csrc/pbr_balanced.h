@@ -65,8 +65,9 @@ constexpr int kBalRec = 7;         // float4 per exchanged pixel record
 // invariants, [9] the exact re-pass barrier; the unbalanced kernel's faithful lean waves: [11] entry to the
 // light loop, [12] the light loop, [13] waves, [14] the barrier, [15] entry to after the barrier
 // Each wave sums its stamps in its own LDS slots (bal_prof, lane 0) and adds them to its own slots of
-// g_bal_prof_buf at the end (plain loads and stores: no contended atomics to perturb the timing).
-__device__ unsigned long long* g_bal_prof_buf;  // 16 per wave, wave = block * 4 + wave in block
+// g_bal_prof_buf at the end (plain loads and stores: no contended atomics to perturb the timing). One copy of the
+// pointer per translation unit: debug_bal_profile (shade_kernels.hip) points every unit's copy at the one buffer.
+static __device__ unsigned long long* g_bal_prof_buf;  // 16 per wave, wave = block * 4 + wave in block
 #define BAL_PROF_T(v) const long long v = (long long)__builtin_amdgcn_s_memtime()
 #define BAL_PROF_ADD(slot_, val_) do { if ((threadIdx.x & 63) == 0) bal_prof[slot_] += (unsigned long long)(val_); } while (0)
 #else

@@ -1,6 +1,6 @@
 // pbr_context.hip -- the C ABI of include/pbr/pbr_shade.h: context lifetime, pass/env upload and
 // the shade entry point (the front end's entry points are in pbr_frontend.hip). Host code only; the kernels live in
-// shade_kernels.hip.
+// shade_kernels.hip and shade_kernels_bal.hip (shade_kernels.h is the interface).
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -10,8 +10,8 @@
 #include "pbr_debug_bounds.h"
 #include "pbr_build_info.h"
 
-// The build records of the library's units (pbr_build_info.h). Weak: a profiling build compiles the balanced kernels
-// into shade_kernels.hip's unit, so shade_kernels_bal's record is then absent (null) and not listed.
+// The build records of the library's units (pbr_build_info.h). Weak: a library linked without one of the units lists
+// the records it has (an absent one is null).
 extern "C" {
 extern const char pbr_unit_info_shade_kernels[] __attribute__((weak));
 extern const char pbr_unit_info_shade_kernels_bal[] __attribute__((weak));
@@ -50,7 +50,7 @@ namespace {
 constexpr float kQuarterStrengthLo = 0x1p-34f, kQuarterStrengthHi = 0x1p50f;
 
 // PBR_FLAG_FAITHFUL forms X (s (att N.L / 4)) per term, skips back-faced items (pbr_balanced.h) and keeps a pixel
-// whose sum is 0 or inside [2^-100, 2^100] (shade_kernels.hip, the sum window). Every strength component of every
+// whose sum is 0 or inside [2^-100, 2^100] (shade_light_loops.h, lighting_fast's sum window). Every strength component of every
 // light kind must be 0 or inside [Lo, Hi]:
 //  * Hi = 2^50: X s att <= 2^57.1 x 2^50 x 2^13.3 stays finite, so the reference's (X (s att)) N.L is not NaN for a
 //    term with N.L = 0 (inf x 0), which the faithful loops evaluate as s x 0 = 0 or skip. (A strength of 3e38 half a
@@ -67,7 +67,7 @@ constexpr float kQuarterStrengthLo = 0x1p-34f, kQuarterStrengthHi = 0x1p50f;
 //    lifted past 2^-100 by a strength near Hi): NOT covered by this gate (residues; not measured).
 constexpr float kFaithfulStrengthLo = 0x1p-25f, kFaithfulStrengthHi = 0x1p50f;
 
-// The faithful finish's Reinhard is c x v_rcp_f32(c + 1) (shade_kernels.hip, reinhard_faithful), and gfx950's v_rcp_f32
+// The faithful finish's Reinhard is c x v_rcp_f32(c + 1) (shade_pixel.h, reinhard_faithful), and gfx950's v_rcp_f32
 // returns 0 where the reciprocal is subnormal (c + 1 >= 2^126: the output was 0 where the reference has ~1). The light
 // sum is within 2^100 (the sum window) and an in-window albedo within 2^10, so a constant ambient colour within 2^100
 // keeps c + 1 below 2^111. The IBL ambient is kD (irradiance albedo) with kD in [0, 1] in a faithful wave (F0 in [0, 1])

@@ -324,7 +324,7 @@ def test_balanced_light_outside_window_sends_all_to_exact(ctx_pair, gpu):
 @pytest.mark.parametrize("mode", MODES)
 @pytest.mark.parametrize("n_on_light", [1, 3, 8, 9, 20, 64])
 def test_balanced_repass_after_stores(n_on_light, mode, ctx_pair, gpu):
-    """The balanced kernels re-pass their exact pixels after the wave's stores (shade_kernels.hip, repass_exact):
+    """The balanced kernels re-pass their exact pixels after the wave's stores (shade_pixel.h, repass_exact):
     up to kLanesRepassMax (8) pixels one at a time with the lanes splitting the lights, more with every lane
     taking its own pixels. Pixels placed exactly on a light (the reference's L = 0 / 0: NaN, absorbed by the
     maxNum clamps; the balanced pass's distance window sends them to the re-pass) in one wave of 128 pixels, the

@@ -1,4 +1,4 @@
-"""The diffuse-IBL ambient's rare and special normals on the GPU (csrc/shade_kernels.hip ambient_ibl_pair).
+"""The diffuse-IBL ambient's rare and special normals on the GPU (csrc/shade_pixel.h ambient_ibl_pair).
 
 WorldToSkyUV's pair forms run a main path for ordinary normals; a zero component, an exponent-gap shortcut, a
 quotient at or above 2^25 and |N.y| == 1 are patched inside a wave-uniform branch; NaN, out-of-window components and

@@ -1,4 +1,4 @@
-"""The lean pair kernel (shade_lean_kernel, shade_kernels.hip).
+"""The lean pair kernel (shade_lean_kernel, shade_lean_kernel.h).
 
 Uniform-loop passes without a sky pass run the lean kernel: the monolithic kernel's per-wave choice of fast
 loops, every settled pixel finished and stored, then, per pixel, the IEEE path for the pixels the fast loop

@@ -121,7 +121,7 @@ def cull_tile():
 
 
 def host_tile_survivors(planes, lights, tile_w, tile_h):
-    """The kernel's per-tile range test (shade_kernels.hip, stage_chunk) emulated in float32: box
+    """The kernel's per-tile range test (shade_light_loops.h, stage_chunk) emulated in float32: box
     distance per axis with maxNum, (dx*dx + dy*dy) + dz*dz rounded per operation, <= 100.01f^2."""
     h, w = planes.shape[1:]
     th, tw = -(-h // tile_h), -(-w // tile_w)

@@ -30,6 +30,8 @@ def test_the_in_tree_library_is_the_product_build_of_this_checkout():
     assert N.build_problems(info) == []
     sk = next(u for u in info["units"] if u["unit"] == "shade_kernels")
     assert sk["switches"]["PBR_X2_MIN_WAVES"] == "4" and sk["switches"]["PBR_DEBUG_BOUNDS"] == "0"
+    for u in info["units"]:  # the removed development switches and the old unit lattice are in no unit's record
+        assert not {"PBR_LEAN_TILES", "PBR_BAL_WAVES", "PBR_SPLIT_BAL"} & set(u["switches"]), u["unit"]
     assert "max-ilp" in sk["cflags"]  # the unit's own scheduler flag is recorded
     fk = next(u for u in info["units"] if u["unit"] == "frontend_kernels")
     assert "max-ilp" in fk["cflags"] and fk["switches"]["PBR_DEBUG_BOUNDS"] == "0"  # the front end keeps that scheduler

@@ -2,9 +2,12 @@
 
 Needs a library built with -DPBR_BAL_PROFILE=1 (make -C physically_based_renderer_amd/csrc EXTRA=...),
 passed as PBR_LIB_PATH. Shades config `--config` (faithful) `--reps` times and prints the average shader
-cycles per balanced wave in each phase, the pass-2 iterations per wave, and the whole kernel per wave.
+cycles per balanced wave in each phase, the pass-2 iterations per wave, and the whole kernel per wave. The
+unbalanced rows are stamped by shade_tile_kernel<.., 0> only: PBR_BALANCED_MIN=0 turns the balanced lists off, and
+PBR_LEAN=0 keeps the pass off shade_lean_kernel, which carries no stamps (every row prints 0 without it).
 
     PBR_LIB_PATH=build/ab/balprof.so python tools/bal_profile.py --config 3
+    PBR_LIB_PATH=build/ab/balprof.so PBR_BALANCED_MIN=0 PBR_LEAN=0 python tools/bal_profile.py --config 2
 """
 import argparse
 import ctypes

@@ -5,7 +5,7 @@ Needs a library built with -DPBR_WAVE_TIMELINE=1, passed as PBR_LIB_PATH:
     make -C physically_based_renderer_amd/csrc OUTDIR=$PWD/build/tl OBJDIR=$PWD/build/tl/obj EXTRA=-DPBR_WAVE_TIMELINE=1
     PBR_LIB_PATH=build/tl/libpbrshade.so python tools/wave_timeline.py --config 2 [--mode faithful] [--json out]
 
-Stamps (shade_kernels.hip, PBR_WAVE_TIMELINE): s_memrealtime (100 MHz, chip-wide) at entry, when the pair's
+Stamps (csrc/shade_wave_timeline.h, PBR_WAVE_TIMELINE): s_memrealtime (100 MHz, chip-wide) at entry, when the pair's
 planes have arrived (s_waitcnt vmcnt(0) in the debug build), at the start and end of the light loops and after
 the stores are issued; HW_ID / XCC_ID name the SIMD and wave slot.
 """
