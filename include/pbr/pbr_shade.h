@@ -437,8 +437,19 @@ int pbr_last_raster_stats(pbr_context* ctx, pbr_raster_stats* out, void* stream)
  * names apply to it -- except that it keeps its source triangle's place in the equal-depth order; `triangles` counts
  * source triangles, so triangles + clip_pieces - clipped_near = the triangles and pieces that reach coverage +
  * backface_culled + zero_area + skipped_near + skipped_guard_band. Arguments, stream rules, errors and scratch as pbr_rasterize; an unknown flag bit, or more than
- * 2^31 - 1 triangles in a clipping call: PBR_ERR_INVALID_ARGUMENT. */
-enum { PBR_RASTER_CLIP_NEAR = 1u << 0 };
+ * 2^31 - 1 triangles in a clipping call: PBR_ERR_INVALID_ARGUMENT.
+ * PBR_RASTER_ALPHA_TEST (RenderLayer::AlphaTested, PBRApp.cpp:308-311; clip(fragOpacity - 0.1f), Default.hlsl:111-113;
+ * detect by the symbol pbr_last_raster_alpha_stats, PBR_ABI_VERSION stays 9): the fragments of every draw whose
+ * `material` is below the table's count and whose pbr_material has PBR_MAT_ALPHA_TEST are tested before the depth
+ * update: the fragment's TexCoord is interpolated as the resolve kernel does for the pixel, the opacity texture's texel
+ * is the point-wrap tap pbr_resolve_materials takes, and with (float)red / 255.0f - 0.1f < 0.0f (bytes 0..25) the
+ * fragment is discarded: it takes no part in the depth test, so whatever lies behind it, geometry or background, shows.
+ * Fragments of other draws (a material id >= the table's count included) are never tested. Needs pbr_set_materials
+ * (PBR_ERR_NOT_READY before it); the call reads the material table and the texels under pbr_resolve_materials's rules:
+ * a later pbr_set_materials on any stream releases them after the queued rasterisations that read them.
+ * pbr_raster_stats.fragments keeps counting discarded fragments. The flag combines with PBR_RASTER_CLIP_NEAR. Bit 1 is
+ * not assigned: a flags word with it is refused like any unknown bit. */
+enum { PBR_RASTER_CLIP_NEAR = 1u << 0, PBR_RASTER_ALPHA_TEST = 1u << 2 };
 int pbr_rasterize_flags(pbr_context* ctx, const pbr_draw* draws, int32_t n_draws, const pbr_raster_view* view,
                         const pbr_raster_targets* targets, uint32_t flags, void* stream);
 
@@ -450,6 +461,15 @@ typedef struct pbr_raster_clip_stats {
 /* The clipping counters of the last rasterisation on `stream` (synchronises it, like pbr_last_raster_stats); zeros
  * after an unflagged call and when the context has not rasterised on that stream. */
 int pbr_last_raster_clip_stats(pbr_context* ctx, pbr_raster_clip_stats* out, void* stream);
+
+typedef struct pbr_raster_alpha_stats {
+    int64_t alpha_tested;    /* fragments (coverage passed, 0 <= z < 1) of tested draws: those that reached the test */
+    int64_t alpha_discarded; /* those the test killed: depth updates issued = fragments - alpha_discarded */
+} pbr_raster_alpha_stats;
+
+/* The alpha-test counters of the last rasterisation on `stream` (synchronises it, like pbr_last_raster_clip_stats);
+ * zeros after a call without PBR_RASTER_ALPHA_TEST and when the context has not rasterised on that stream. */
+int pbr_last_raster_alpha_stats(pbr_context* ctx, pbr_raster_alpha_stats* out, void* stream);
 
 /* ---- Host G-buffer fill (replaces the VS + rasteriser front-end, Default.hlsl:22-45) ---------- */
 

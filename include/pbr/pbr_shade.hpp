@@ -383,8 +383,9 @@ class ShadingContext {
     // VS + the rasteriser (Default.hlsl:22-45, DrawIndexedInstanced): `draws` in order under `view`
     // into rows [view.row_begin, view.row_end) of `attrs` (a full-frame buffer), with an optional depth plane of
     // attrs' row stride holding the same rows.
-    // `flags`: 0 (pbr_rasterize) or PBR_RASTER_CLIP_NEAR (pbr_rasterize_flags: triangles are clipped against the near
-    // plane, not skipped).
+    // `flags`: 0 (pbr_rasterize) or, through pbr_rasterize_flags, PBR_RASTER_CLIP_NEAR (triangles are clipped against
+    // the near plane, not skipped) and / or PBR_RASTER_ALPHA_TEST (fragments of PBR_MAT_ALPHA_TEST materials are
+    // discarded before the depth update where the opacity texture says so; needs SetMaterials).
     void Rasterize(const std::vector<pbr_draw>& draws, const pbr_raster_view& view, DeviceAttributes& attrs,
                    float* depth = nullptr, hipStream_t stream = nullptr, uint32_t flags = 0) {
         const pbr_attributes_soa band = attrs.Band(view.row_begin, view.row_end);
@@ -410,6 +411,11 @@ class ShadingContext {
     pbr_raster_clip_stats LastRasterClipStats(hipStream_t stream = nullptr) {
         pbr_raster_clip_stats s;
         Check(pbr_last_raster_clip_stats(ctx_, &s, stream), "pbr_last_raster_clip_stats");
+        return s;
+    }
+    pbr_raster_alpha_stats LastRasterAlphaStats(hipStream_t stream = nullptr) {
+        pbr_raster_alpha_stats s;
+        Check(pbr_last_raster_alpha_stats(ctx_, &s, stream), "pbr_last_raster_alpha_stats");
         return s;
     }
     pbr_raster_stats LastRasterStats(hipStream_t stream = nullptr) {

@@ -250,12 +250,20 @@ class RasterStats(ctypes.Structure):
 
 
 PBR_RASTER_CLIP_NEAR = 1 << 0
+PBR_RASTER_ALPHA_TEST = 1 << 2  # bit 1 is not assigned
 
 
 class RasterClipStats(ctypes.Structure):
     _fields_ = [
         ("clipped_near", ctypes.c_int64),
         ("clip_pieces", ctypes.c_int64),
+    ]
+
+
+class RasterAlphaStats(ctypes.Structure):
+    _fields_ = [
+        ("alpha_tested", ctypes.c_int64),
+        ("alpha_discarded", ctypes.c_int64),
     ]
 
 
@@ -318,6 +326,8 @@ SIGNATURES = {
                                            ctypes.POINTER(RasterView), ctypes.POINTER(RasterTargets), ctypes.c_uint32,
                                            ctypes.c_void_p]),
     "pbr_last_raster_clip_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(RasterClipStats), ctypes.c_void_p]),
+    "pbr_last_raster_alpha_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(RasterAlphaStats),
+                                                   ctypes.c_void_p]),
     "pbr_attributes_fill": (ctypes.c_int64, [ctypes.POINTER(SceneDesc), ctypes.c_int32, ctypes.c_int32,
                                              ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.c_int64,
                                              ctypes.c_int32]),

@@ -69,10 +69,11 @@ struct RasterVertex {
     uint32_t flags;  // kVertexNear: w not > 0; kVertexGuard: beyond the guard band or not finite; kVertexOutside
     uint32_t pad;
 };
-// Counters of a call, unsigned 64-bit words in device memory (pbr_raster_stats, pbr_raster_clip_stats; kRasterLarge:
-// the large-triangle list's length).
+// Counters of a call, unsigned 64-bit words in device memory (pbr_raster_stats, pbr_raster_clip_stats,
+// pbr_raster_alpha_stats; kRasterLarge: the large-triangle list's length). The first eight keep their slots.
 enum RasterCounter { kRasterLarge = 0, kRasterCulled, kRasterZeroArea, kRasterNear, kRasterGuard, kRasterFragments,
-                     kRasterClipped, kRasterClipPieces, kRasterCounters = 8 };
+                     kRasterClipped, kRasterClipPieces, kRasterAlphaTested, kRasterAlphaDiscarded,
+                     kRasterCounters = 10 };
 
 struct RasterArgs {
     const float* vertices;    // the mesh set: 14 floats per vertex
@@ -99,10 +100,17 @@ struct RasterArgs {
     bool clip_near;    // PBR_RASTER_CLIP_NEAR: the launches below start the kernels' clipping instantiations
     float4* posh;      // clip_near: PosH of every vertex record (n_records); else nullptr
     int64_t n_large;   // slots of `large`: n_tris, 2 n_tris when clip_near (a clipped triangle has up to two pieces)
+    // Appended for PBR_RASTER_ALPHA_TEST (step 6a), read by the ALPHA instantiations only.
+    const MaterialRec* table;  // the context's material table
+    int n_materials;
+    const uint32_t* texels;    // every texture, RGBA8
+    int64_t n_texels;
+    bool alpha_test;   // some draw's material has kMatAlphaTest: setup and large launch their ALPHA instantiations
 };
 // The stages of pbr_rasterize, each one launch (none when it has nothing to do): the vertex transform, the triangle
 // setup with the small triangles' coverage, the large triangles' coverage, the per-pixel resolve. With a.clip_near
-// each launches its near-clipping instantiation.
+// each launches its near-clipping instantiation; with a.alpha_test the setup and the
+// large-triangle stage launch their alpha-testing instantiations (step 6a).
 hipError_t launch_raster_vertices(const RasterArgs& a, hipStream_t stream);
 hipError_t launch_raster_setup(const RasterArgs& a, hipStream_t stream);
 hipError_t launch_raster_large(const RasterArgs& a, hipStream_t stream);

@@ -94,13 +94,16 @@ struct pbr_context {
         explicit Texture(std::vector<Resource*>& l) : use(l, &d_u16, &d) {}
     };
     Texture env{resources}, sky{resources};
-    // The material table and its textures (pbr_set_materials; read by pbr_resolve_materials): the records and one
-    // RGBA8 texel buffer holding every texture, replaced as a whole.
+    // The material table and its textures (pbr_set_materials; read by pbr_resolve_materials and by a
+    // pbr_rasterize_flags with PBR_RASTER_ALPHA_TEST): the records and one RGBA8 texel buffer holding every texture,
+    // replaced as a whole; the records' flags stay on the host as well, where the rasteriser looks whether a call
+    // draws a tested material at all.
     struct Materials {
         pbr::MaterialRec* d_table = nullptr;
         uint32_t* d_texels = nullptr;
         int n = 0;
         int64_t n_texels = 0;
+        std::vector<uint32_t> flags;  // n
         bool set = false;
         Resource use;
         explicit Materials(std::vector<Resource*>& l) : use(l, &d_table, &d_texels) {}

@@ -90,6 +90,8 @@ int pbr_set_materials(pbr_context* ctx, const pbr_material* materials, int32_t n
         return rc;
     mt.n = n_materials;
     mt.n_texels = (int64_t)texels.size();
+    mt.flags.resize((size_t)n_materials);
+    for (int32_t i = 0; i < n_materials; ++i) mt.flags[(size_t)i] = materials[i].flags;
     mt.set = true;
     return PBR_OK;
 }
@@ -232,7 +234,7 @@ namespace {
 int rasterize_impl(pbr_context* ctx, const pbr_draw* draws, int32_t n_draws, const pbr_raster_view* view,
                    const pbr_raster_targets* tg, uint32_t flags, void* stream, hipEvent_t* marks) {
     if (!ctx || !view || !tg || n_draws < 0 || (n_draws > 0 && !draws)) return PBR_ERR_INVALID_ARGUMENT;
-    if (flags & ~(uint32_t)PBR_RASTER_CLIP_NEAR) return PBR_ERR_INVALID_ARGUMENT;
+    if (flags & ~(uint32_t)(PBR_RASTER_CLIP_NEAR | PBR_RASTER_ALPHA_TEST)) return PBR_ERR_INVALID_ARGUMENT;
     const bool clip_near = (flags & PBR_RASTER_CLIP_NEAR) != 0;
     if (view->width < 0 || view->height < 0 || view->width > kRasterMaxSide || view->height > kRasterMaxSide)
         return PBR_ERR_INVALID_ARGUMENT;
@@ -265,6 +267,14 @@ int rasterize_impl(pbr_context* ctx, const pbr_draw* draws, int32_t n_draws, con
     Entry en(ctx);
     const pbr_context::Meshes& ms = ctx->meshes;
     if (!ms.set) return PBR_ERR_NOT_READY;
+    // PBR_RASTER_ALPHA_TEST: the alpha-testing kernels run, and the call reads the material table and the texels,
+    // only when some draw's material is tested; the flag alone costs nothing on a scene without cut-outs.
+    const pbr_context::Materials& mt = ctx->mats;
+    if ((flags & PBR_RASTER_ALPHA_TEST) && !mt.set) return PBR_ERR_NOT_READY;
+    bool alpha_test = false;
+    if (flags & PBR_RASTER_ALPHA_TEST)
+        for (int32_t i = 0; i < n_draws && !alpha_test; ++i)
+            alpha_test = draws[i].material < (uint32_t)mt.n && (mt.flags[draws[i].material] & PBR_MAT_ALPHA_TEST) != 0;
     uint64_t n_tris = 0, n_records = 0;
     for (int32_t i = 0; i < n_draws; ++i) {
         const pbr_draw& d = draws[i];
@@ -357,8 +367,18 @@ int rasterize_impl(pbr_context* ctx, const pbr_draw* draws, int32_t n_draws, con
     a.indices = ms.d_indices;
     a.n_src_vertices = ms.n_vertices;
     a.n_src_indices = debug_bounds_skew() ? 0 : ms.n_indices;
+    a.alpha_test = alpha_test;
+    if (alpha_test) {
+        a.table = mt.d_table;
+        a.n_materials = mt.n;
+        a.texels = mt.d_texels;
+        a.n_texels = debug_bounds_skew() ? 0 : mt.n_texels;
+    }
 
     e = before_read(ctx->meshes.use, s, si);
+    // A reader of the material table and the texels like pbr_resolve_materials: a later pbr_set_materials on any stream
+    // releases them after this call (after_launch below records the event it waits for).
+    if (e == hipSuccess && alpha_test) e = before_read(ctx->mats.use, s, si);
     if (e != hipSuccess) return fail_hip(ctx, e, "pbr_rasterize order");
     auto mark = [&](int i) { return marks ? hipEventRecord(marks[i], s) : hipSuccess; };
     (void)mark(0);
@@ -453,6 +473,18 @@ int pbr_last_raster_clip_stats(pbr_context* ctx, pbr_raster_clip_stats* out, voi
     if (const int rc = read_raster_counters(ctx, stream, h, &triangles, &ran, "pbr_last_raster_clip_stats")) return rc;
     out->clipped_near = (int64_t)h[pbr::kRasterClipped];
     out->clip_pieces = (int64_t)h[pbr::kRasterClipPieces];
+    return PBR_OK;
+}
+
+int pbr_last_raster_alpha_stats(pbr_context* ctx, pbr_raster_alpha_stats* out, void* stream) {
+    if (!ctx || !out) return PBR_ERR_INVALID_ARGUMENT;
+    *out = pbr_raster_alpha_stats{};
+    unsigned long long h[pbr::kRasterCounters] = {};  // every call clears them: zeros unless fragments were tested
+    int64_t triangles = 0;
+    bool ran = false;
+    if (const int rc = read_raster_counters(ctx, stream, h, &triangles, &ran, "pbr_last_raster_alpha_stats")) return rc;
+    out->alpha_tested = (int64_t)h[pbr::kRasterAlphaTested];
+    out->alpha_discarded = (int64_t)h[pbr::kRasterAlphaDiscarded];
     return PBR_OK;
 }
 

@@ -29,10 +29,19 @@
 // same operations (piece_setup), so the resolve reproduces the key's z bits as it does for an unclipped triangle. A
 // large-list entry carries the piece's number in the top bit of its block count (a block count is below 2^23: frames
 // are at most 32,768 on a side).
+//
+// The alpha test (pbr_rasterize_flags with PBR_RASTER_ALPHA_TEST; RenderLayer::AlphaTested,
+// Default.hlsl:111-113) is a further instantiation (template parameter ALPHA) of the kernels that run the coverage test
+// -- the two setup kernels and the large-triangle kernel -- launched only when some draw of a flagged call has a
+// material with PBR_MAT_ALPHA_TEST; the ALPHA = false instantiations are the kernels of an unflagged call, instruction
+// for instruction. A fragment of a tested draw interpolates its TexCoord with the resolve's operations, fetches the
+// material resolve's point-wrap tap of the opacity texture and, with opacity - 0.1 < 0, issues no visibility update.
+// The vertex and resolve kernels do not change: the winner is still the key's triangle.
 #pragma once
 
 #include "pbr_device_math.h"
 #include "frontend_kernels.h"
+#include "material_resolve.h"
 
 namespace pbr {
 
@@ -219,6 +228,90 @@ __device__ __forceinline__ void load_z(const RasterArgs& a, const Tri& s, float 
     for (int v = 0; v < 3; ++v) z[v] = a.records[PBR_BOUNDS((int64_t)s.rec[v], (int64_t)a.n_records, kBoundsRaster)].z;
 }
 
+// ---- Alpha test (step 6a; the ALPHA instantiations) ----
+// What the test needs of a triangle (or piece): whether its draw is tested, the opacity texture of the draw's material
+// record, and 1 / w and TexCoord of the three vertices in setup's order. Filled only for a tested draw.
+struct AlphaTri {
+    bool tested;
+    MaterialTex tex;
+    float rw[3], u[3], v[3];
+};
+
+// The draw's material: tested iff its id is inside the table and the record has PBR_MAT_ALPHA_TEST. UNIFORM: the draw
+// is the same over the wave, so the record is read through a wave-uniform index (scalar loads, a uniform branch).
+template <bool UNIFORM>
+__device__ __forceinline__ void alpha_material(const RasterArgs& a, int draw, AlphaTri& al) {
+    uint32_t id = a.draws[PBR_BOUNDS((int64_t)draw, (int64_t)a.n_draws, kBoundsRaster)].material;
+    if constexpr (UNIFORM) id = (uint32_t)__builtin_amdgcn_readfirstlane((int)id);
+    al.tested = false;
+    if (id < (uint32_t)a.n_materials) {
+        const MaterialRec& m = a.table[PBR_BOUNDS((int64_t)id, (int64_t)a.n_materials, kBoundsTexel)];
+        if (m.flags & kMatAlphaTest) {
+            al.tested = true;
+            al.tex = m.tex[5];
+        }
+    }
+}
+
+// rw and TexCoord of a submitted triangle's vertices: their records'.
+__device__ __forceinline__ void alpha_vertices(const RasterArgs& a, const Tri& s, AlphaTri& al) {
+#pragma unroll
+    for (int v = 0; v < 3; ++v) {
+        const RasterVertex& r = a.records[PBR_BOUNDS((int64_t)s.rec[v], (int64_t)a.n_records, kBoundsRaster)];
+        al.rw[v] = r.rw;
+        al.u[v] = r.a[12];
+        al.v[v] = r.a[13];
+    }
+}
+
+// The test of one fragment: TexCoord with the operations of step 8 (the resolve's), the resolve's point-wrap tap of the
+// opacity texture, clip(opacity - 0.1f) (Default.hlsl:111-113). True: the fragment is discarded.
+__device__ __forceinline__ bool alpha_discards(const RasterArgs& a, const AlphaTri& al, const float l[3]) {
+    float p[3], q[3];
+#pragma unroll
+    for (int v = 0; v < 3; ++v) p[v] = l[v] * al.rw[v];
+    const float sum = (p[0] + p[1]) + p[2];
+#pragma unroll
+    for (int v = 0; v < 3; ++v) q[v] = p[v] / sum;
+    const float tu = (q[0] * al.u[0] + q[1] * al.u[1]) + q[2] * al.u[2];
+    const float tv = (q[0] * al.v[0] + q[1] * al.v[1]) + q[2] * al.v[2];
+    const float o = resolve::unorm8(resolve::tap_point(a.texels, a.n_texels, al.tex, tu, tv), 0);
+    return o - 0.1f < 0.0f;
+}
+
+// raster_pixel with step 6a between the depth range and the visibility update. Bit 0: a fragment exists; bit 1: it
+// reached the test; bit 2: the test discarded it (no visibility update).
+constexpr uint32_t kFragment = 1u, kFragTested = 2u, kFragDiscarded = 4u;
+__device__ __forceinline__ uint32_t raster_pixel_alpha(const RasterArgs& a, const Tri& s, const Edges& e,
+                                                       const float z[3], const AlphaTri& al, uint32_t prim, int x,
+                                                       int y) {
+    const long long E[3] = {edge_at(e, 0, x, y), edge_at(e, 1, x, y), edge_at(e, 2, x, y)};
+    if (!covered(e, E)) return 0u;
+    float l[3];
+    barycentrics(E, s.A, l);
+    const float zf = interpolate_z(l, z);
+    if (!(zf >= 0.0f && zf < 1.0f)) return 0u;
+    uint32_t r = kFragment;
+    if (al.tested) {
+        r |= kFragTested;
+        if (alpha_discards(a, al, l)) return r | kFragDiscarded;
+    }
+    const unsigned long long key = ((unsigned long long)__float_as_uint(zf) << 32) | (unsigned long long)prim;
+    [[maybe_unused]] const int64_t n_vis = (int64_t)(a.row_end - a.row_begin) * a.width;
+    atomicMin(a.vis + PBR_BOUNDS((int64_t)(y - a.row_begin) * a.width + x, n_vis, kBoundsRaster), key);
+    return r;
+}
+
+// A lane's (or workgroup's) fragment counts: those that exist, those tested, those discarded.
+struct FragCounts {
+    uint32_t frags = 0, tested = 0, discarded = 0;
+    __device__ __forceinline__ void add(uint32_t r) {
+        frags += r & 1u;
+        tested += (r >> 1) & 1u;
+        discarded += r >> 2;
+    }
+};
+
 // ---- Near-plane clipping (step 2a) ----
 // A piece of a clipped triangle after setup: s as for a triangle, with s.rec[v] the submitted vertex that piece
 // vertex v is (recb[v] == s.rec[v]) or the inside end of the edge whose crossing with z = 0 it is (recb[v]: the outside
@@ -306,6 +399,20 @@ __device__ __forceinline__ TriStatus piece_setup(const RasterArgs& a, const Tri&
     return kTriDraw;
 }
 
+// rw and TexCoord of a piece's vertices (step 6a): the piece's rw; a new vertex's TexCoord is a + t (b - a) of its
+// edge's ends, the operation resolve_clipped interpolates it with.
+__device__ __forceinline__ void alpha_piece_vertices(const RasterArgs& a, const Piece& P, AlphaTri& al) {
+#pragma unroll
+    for (int v = 0; v < 3; ++v) {
+        const RasterVertex& ra = a.records[PBR_BOUNDS((int64_t)P.s.rec[v], (int64_t)a.n_records, kBoundsRaster)];
+        const RasterVertex& rb = a.records[PBR_BOUNDS((int64_t)P.recb[v], (int64_t)a.n_records, kBoundsRaster)];
+        const bool submitted = P.recb[v] == P.s.rec[v];
+        al.rw[v] = P.rw[v];
+        al.u[v] = submitted ? ra.a[12] : ra.a[12] + P.t[v] * (rb.a[12] - ra.a[12]);
+        al.v[v] = submitted ? ra.a[13] : ra.a[13] + P.t[v] * (rb.a[13] - ra.a[13]);
+    }
+}
+
 // Sum over the wave, then one atomic from its first lane. Every lane of the wave calls it.
 __device__ __forceinline__ void count_wave(unsigned long long* counter, uint32_t mine) {
     unsigned long long v = mine;
@@ -383,6 +490,14 @@ __device__ __forceinline__ uint32_t raster_small(const RasterArgs& a, const Tri&
         for (int x = b.x0; x <= b.x1; ++x) frags += raster_pixel(a, s, e, z, prim, x, y);
     return frags;
 }
+// The same with the alpha test (step 6a).
+__device__ __forceinline__ void raster_small_alpha(const RasterArgs& a, const Tri& s, const Box& b, const float z[3],
+                                                   const AlphaTri& al, uint32_t prim, FragCounts& n) {
+    Edges e;
+    tri_edges(s, e);
+    for (int y = b.y0; y <= b.y1; ++y)
+        for (int x = b.x0; x <= b.x1; ++x) n.add(raster_pixel_alpha(a, s, e, z, al, prim, x, y));
+}
 
 // Appends the wave's large triangles (or pieces: `piece` in the top bit of the block count) to the list: one atomic
 // per wave. Every lane of the wave calls it.
@@ -405,7 +520,10 @@ __device__ __forceinline__ void append_large(const RasterArgs& a, bool large, co
 
 }  // namespace raster
 
-// Stage 2: setup of every triangle, the statistics, the small triangles' coverage, the large list.
+// Stage 2: setup of every triangle, the statistics, the small triangles' coverage, the large list. ALPHA (a call with
+// PBR_RASTER_ALPHA_TEST some draw of which has a tested material): each lane has its own triangle, so the material
+// record is read per lane, and rw and TexCoord only by the lane of a small triangle of a tested draw.
+template <bool ALPHA>
 __global__ __launch_bounds__(256) void raster_setup_kernel(const RasterArgs a) {
     using namespace raster;
     const uint32_t t = blockIdx.x * 256u + threadIdx.x;
@@ -423,7 +541,20 @@ __global__ __launch_bounds__(256) void raster_setup_kernel(const RasterArgs a) {
     const bool small = draw && npix <= kSmallPixels, large = draw && !small;
 
     uint32_t frags = 0;
-    if (small) {
+    if constexpr (ALPHA) {
+        FragCounts n;
+        if (small) {
+            float z[3];
+            load_z(a, s, z);
+            AlphaTri al;
+            alpha_material<false>(a, s.draw, al);
+            if (al.tested) alpha_vertices(a, s, al);
+            raster_small_alpha(a, s, b, z, al, t, n);
+        }
+        frags = n.frags;
+        count_wave(a.counters + kRasterAlphaTested, n.tested);
+        count_wave(a.counters + kRasterAlphaDiscarded, n.discarded);
+    } else if (small) {
         Edges e;
         tri_edges(s, e);
         float z[3];
@@ -451,7 +582,9 @@ __global__ __launch_bounds__(256) void raster_setup_kernel(const RasterArgs a) {
 
 // Stage 2 with near clipping: the lane of a clipped triangle walks its (at most two) pieces; each is counted,
 // rasterised or listed as a submitted triangle would be. Both rounds of the piece loop are taken by every lane, so the
-// wave-wide ballots and sums inside it see the whole wave.
+// wave-wide ballots and sums inside it see the whole wave. ALPHA: as in raster_setup_kernel; a piece takes the test with
+// its own rw and its new vertices' TexCoord.
+template <bool ALPHA>
 __global__ __launch_bounds__(256) void raster_setup_clip_kernel(const RasterArgs a) {
     using namespace raster;
     const uint32_t t = blockIdx.x * 256u + threadIdx.x;
@@ -466,6 +599,7 @@ __global__ __launch_bounds__(256) void raster_setup_clip_kernel(const RasterArgs
     // what the triangle itself adds to the skip counters; its pieces add theirs below
     uint32_t culled = st == kTriCulled, zero = st == kTriZeroArea, near = st == kTriNear, guard = st == kTriGuard;
     uint32_t frags = 0;
+    [[maybe_unused]] FragCounts n;
     for (int p = 0; p < 2; ++p) {
         Piece P;
         Box b{0, -1, 0, -1};
@@ -484,27 +618,47 @@ __global__ __launch_bounds__(256) void raster_setup_clip_kernel(const RasterArgs
         const bool small = draw && npix <= kSmallPixels, large = draw && !small;
         if (small) {
             if (!clipped) load_z(a, P.s, P.z);
-            frags += raster_small(a, P.s, b, P.z, t);
+            if constexpr (ALPHA) {
+                AlphaTri al;
+                alpha_material<false>(a, P.s.draw, al);
+                if (al.tested) {
+                    if (clipped)
+                        alpha_piece_vertices(a, P, al);
+                    else
+                        alpha_vertices(a, P.s, al);
+                }
+                raster_small_alpha(a, P.s, b, P.z, al, t, n);
+            } else {
+                frags += raster_small(a, P.s, b, P.z, t);
+            }
         }
         append_large(a, large, b, t, (uint32_t)p, a.n_large);
     }
+    if constexpr (ALPHA) frags = n.frags;
     count_wave(a.counters + kRasterCulled, culled);
     count_wave(a.counters + kRasterZeroArea, zero);
     count_wave(a.counters + kRasterNear, near);
     count_wave(a.counters + kRasterGuard, guard);
     count_wave(a.counters + kRasterFragments, frags);
+    if constexpr (ALPHA) {
+        count_wave(a.counters + kRasterAlphaTested, n.tested);
+        count_wave(a.counters + kRasterAlphaDiscarded, n.discarded);
+    }
 }
 
 // Stage 3: the large triangles. blockIdx.x strides over the list, blockIdx.y over the triangle's 64 x 4 blocks; a wave
 // is one row of a block. All control flow outside the pixel test is uniform over the workgroup. CLIP: an entry names a
 // triangle or, with the piece's number in the top bit of its block count, a piece of a clipped one.
-template <bool CLIP>
+// ALPHA: the workgroup's triangle has one draw, so its material record and the "tested" decision are wave-uniform: the
+// record arrives by scalar loads and the test's branch is uniform; only the texel fetch is per lane.
+template <bool CLIP, bool ALPHA>
 __global__ __launch_bounds__(256) void raster_large_kernel(const RasterArgs a) {
     using namespace raster;
     const unsigned long long listed = a.counters[kRasterLarge];
     const uint32_t slots = CLIP ? (uint32_t)a.n_large : a.n_tris;
     const uint32_t n_large = listed < (unsigned long long)slots ? (uint32_t)listed : slots;
     uint32_t frags = 0;
+    [[maybe_unused]] FragCounts n;
     for (uint32_t i = blockIdx.x; i < n_large; i += gridDim.x) {
         const uint2 entry = a.large[PBR_BOUNDS((int64_t)i, (int64_t)slots, kBoundsRaster)];
         const uint32_t blocks = CLIP ? entry.y & 0x7FFFFFFFu : entry.y;
@@ -513,18 +667,24 @@ __global__ __launch_bounds__(256) void raster_large_kernel(const RasterArgs a) {
         Tri s;
         Box b;
         float z[3];
+        [[maybe_unused]] AlphaTri al;
         if constexpr (CLIP) {
             uint32_t outside = 0;
             const TriStatus st = tri_setup<true>(a, t, s, &outside);
+            if constexpr (ALPHA) alpha_material<true>(a, s.draw, al);
             if (st == kTriClipped) {
                 Piece P;
                 if (piece_setup(a, s, outside, (int)(entry.y >> 31), P) != kTriDraw) continue;  // never, as below
                 s = P.s;
 #pragma unroll
                 for (int v = 0; v < 3; ++v) z[v] = P.z[v];
+                if constexpr (ALPHA)
+                    if (al.tested) alpha_piece_vertices(a, P, al);
             } else {
                 if (st != kTriDraw) continue;
                 load_z(a, s, z);
+                if constexpr (ALPHA)
+                    if (al.tested) alpha_vertices(a, s, al);
             }
             if (!tri_box(a, s, b)) continue;
         } else {
@@ -536,6 +696,10 @@ __global__ __launch_bounds__(256) void raster_large_kernel(const RasterArgs a) {
         Edges e;
         tri_edges(s, e);
         if constexpr (!CLIP) load_z(a, s, z);
+        if constexpr (!CLIP && ALPHA) {
+            alpha_material<true>(a, s.draw, al);
+            if (al.tested) alpha_vertices(a, s, al);
+        }
         for (uint32_t blk = blockIdx.y; blk < nb; blk += gridDim.y) {
             const int X0 = b.x0 + (int)(blk % nbx) * kBlockW, Y0 = b.y0 + (int)(blk / nbx) * kBlockH;
             const int X1 = min(X0 + kBlockW - 1, b.x1), Y1 = min(Y0 + kBlockH - 1, b.y1);
@@ -548,10 +712,19 @@ __global__ __launch_bounds__(256) void raster_large_kernel(const RasterArgs a) {
             }
             if (reject) continue;
             const int x = X0 + (int)(threadIdx.x & 63u), y = Y0 + (int)(threadIdx.x >> 6);
-            if (x <= X1 && y <= Y1) frags += raster_pixel(a, s, e, z, t, x, y);
+            if constexpr (ALPHA) {
+                if (x <= X1 && y <= Y1) n.add(raster_pixel_alpha(a, s, e, z, al, t, x, y));
+            } else {
+                if (x <= X1 && y <= Y1) frags += raster_pixel(a, s, e, z, t, x, y);
+            }
         }
     }
+    if constexpr (ALPHA) frags = n.frags;
     count_wave(a.counters + kRasterFragments, frags);
+    if constexpr (ALPHA) {
+        count_wave(a.counters + kRasterAlphaTested, n.tested);
+        count_wave(a.counters + kRasterAlphaDiscarded, n.discarded);
+    }
 }
 
 namespace raster {
@@ -717,10 +890,16 @@ hipError_t launch_raster_vertices(const RasterArgs& a, hipStream_t stream) {
 hipError_t launch_raster_setup(const RasterArgs& a, hipStream_t stream) {
     if (a.n_tris == 0u) return hipSuccess;
     const dim3 grid((uint32_t)(((uint64_t)a.n_tris + 255u) / 256u));
-    if (a.clip_near)
-        hipLaunchKernelGGL(raster_setup_clip_kernel, grid, dim3(256), 0, stream, a);
-    else
-        hipLaunchKernelGGL(raster_setup_kernel, grid, dim3(256), 0, stream, a);
+    if (a.clip_near) {
+        if (a.alpha_test)
+            hipLaunchKernelGGL((raster_setup_clip_kernel<true>), grid, dim3(256), 0, stream, a);
+        else
+            hipLaunchKernelGGL((raster_setup_clip_kernel<false>), grid, dim3(256), 0, stream, a);
+    } else if (a.alpha_test) {
+        hipLaunchKernelGGL((raster_setup_kernel<true>), grid, dim3(256), 0, stream, a);
+    } else {
+        hipLaunchKernelGGL((raster_setup_kernel<false>), grid, dim3(256), 0, stream, a);
+    }
     return hipGetLastError();
 }
 
@@ -728,10 +907,16 @@ hipError_t launch_raster_large(const RasterArgs& a, hipStream_t stream) {
     if (a.n_tris == 0u) return hipSuccess;
     const uint32_t gx = a.n_tris < (uint32_t)raster::kLargeGridX ? a.n_tris : (uint32_t)raster::kLargeGridX;
     const dim3 grid(gx, raster::kLargeSlabs);
-    if (a.clip_near)
-        hipLaunchKernelGGL((raster_large_kernel<true>), grid, dim3(256), 0, stream, a);
-    else
-        hipLaunchKernelGGL((raster_large_kernel<false>), grid, dim3(256), 0, stream, a);
+    if (a.clip_near) {
+        if (a.alpha_test)
+            hipLaunchKernelGGL((raster_large_kernel<true, true>), grid, dim3(256), 0, stream, a);
+        else
+            hipLaunchKernelGGL((raster_large_kernel<true, false>), grid, dim3(256), 0, stream, a);
+    } else if (a.alpha_test) {
+        hipLaunchKernelGGL((raster_large_kernel<false, true>), grid, dim3(256), 0, stream, a);
+    } else {
+        hipLaunchKernelGGL((raster_large_kernel<false, false>), grid, dim3(256), 0, stream, a);
+    }
     return hipGetLastError();
 }
 

@@ -445,14 +445,17 @@ class ShadingContext:
         self.meshes = meshes
 
     def rasterize(self, draws: Sequence[Draw], view: View, out=None, stream=None,
-                  clip_near: bool = False) -> Attributes:
+                  clip_near: bool = False, alpha_test: bool = False) -> Attributes:
         """VS and the rasteriser on the device (pbr_rasterize): ``draws`` in order under ``view`` into
         the attribute planes :meth:`resolve` consumes, asynchronously. ``out``: an ``Attributes`` holding the view's
         row band, or an ``(Attributes, depth)`` pair with an (H, row_stride) float32 depth plane; default: fresh
         tensors. The result carries the depth plane as ``.depth`` (None when ``out`` had none). ``clip_near``
         (pbr_rasterize_flags with PBR_RASTER_CLIP_NEAR): triangles that cross the near plane are clipped against it
-        and drawn, not skipped (step 2a)."""
-        return self.rasterize_flags(draws, view, N.PBR_RASTER_CLIP_NEAR if clip_near else None, out=out, stream=stream)
+        and drawn, not skipped (step 2a). ``alpha_test`` (PBR_RASTER_ALPHA_TEST; needs :meth:`set_materials`): the
+        fragments of draws whose material has PBR_MAT_ALPHA_TEST are discarded before the depth update where the
+        opacity texture's texel is below the threshold, so what lies behind a cut-out shows (step 6a)."""
+        flags = (N.PBR_RASTER_CLIP_NEAR if clip_near else 0) | (N.PBR_RASTER_ALPHA_TEST if alpha_test else 0)
+        return self.rasterize_flags(draws, view, flags if flags else None, out=out, stream=stream)
 
     def rasterize_flags(self, draws: Sequence[Draw], view: View, flags, out=None, stream=None) -> Attributes:
         """:meth:`rasterize` through pbr_rasterize_flags with the given ``flags`` word (0: the same result as
@@ -507,6 +510,14 @@ class ShadingContext:
         N.check(self.lib.pbr_last_raster_clip_stats(self._h, ctypes.byref(st), ctypes.c_void_p(_stream_handle(stream))),
                 "pbr_last_raster_clip_stats", self._h)
         return {name: getattr(st, name) for name, _ in N.RasterClipStats._fields_}
+
+    def raster_alpha_stats(self, stream=None) -> dict:
+        """pbr_last_raster_alpha_stats of the last :meth:`rasterize` on ``stream`` (synchronises it): alpha_tested,
+        alpha_discarded; zeros after a call without ``alpha_test``."""
+        st = N.RasterAlphaStats()
+        N.check(self.lib.pbr_last_raster_alpha_stats(self._h, ctypes.byref(st), ctypes.c_void_p(_stream_handle(stream))),
+                "pbr_last_raster_alpha_stats", self._h)
+        return {name: getattr(st, name) for name, _ in N.RasterAlphaStats._fields_}
 
     def _check_device(self, *tensors) -> None:
         """Every tensor handed to the kernel must live on this context's device: a foreign pointer would be

@@ -5,7 +5,9 @@
   stress       ~10^6 triangles of about a pixel, uniformly over the frame;
   walkthrough  the reference scene over a floor of 64 x 64 quads, the eye one unit above the floor between the spheres
                of the bottom row: spheres and floor cross the near plane. Only near-plane clipping
-               (pbr_rasterize_flags with PBR_RASTER_CLIP_NEAR) draws those triangles.
+               (pbr_rasterize_flags with PBR_RASTER_CLIP_NEAR) draws those triangles;
+  cutout       the reference scene with all 58 spheres under one alpha-tested material whose opacity map is a
+               256 x 256 checker with noise (libraries with PBR_RASTER_ALPHA_TEST only).
 
 Four legs per scene:
   (a) the stages of one call, HIP events between them (pbr_debug_rasterize_timed): clears and table upload, the
@@ -17,7 +19,9 @@ Four legs per scene:
   (d) reference scene only: the host route to the same planes, pbr_attributes_fill on 16 threads plus the upload
       (the analytic spheres, not the facets: DESIGN.md §12).
 Legs (a) and (b) are taken unflagged and then, when the library has pbr_rasterize_flags, with PBR_RASTER_CLIP_NEAR
-("clip": true in the line), with the clip counters of the call.
+("clip": true in the line), with the clip counters of the call; and, when it has PBR_RASTER_ALPHA_TEST, with that flag
+("alpha": true) and the alpha counters: on the first three scenes under a table without a tested material (the cost
+of asking), on cutout against the same scene unflagged (the cost of the test).
 
     python tools/raster_bench.py [--width 3840 --height 2160] [--steps 50] [--log profiles/r11/raster_bench.log]
 
@@ -38,7 +42,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from physically_based_renderer_amd import _native as N  # noqa: E402
 from physically_based_renderer_amd import scenes as S  # noqa: E402
-from physically_based_renderer_amd.renderer import Attributes, Draw, Mesh, ShadingContext, View  # noqa: E402
+from physically_based_renderer_amd.renderer import Attributes, Draw, Material, Mesh, ShadingContext, View  # noqa: E402
 
 STAGES = ("clear_upload", "vertex", "setup_small", "large", "resolve")
 BYTES_WRITTEN = 14 * 4 + 2
@@ -98,16 +102,28 @@ def walkthrough_scene(W, H, slices, stacks, quads=64):
     return meshes, draws, view
 
 
-def timed_stages(ctx, draws, view, attrs, depth, steps, clip=False):
+def cutout_materials(n, seed=12):
+    """n alpha-tested materials over one 256 x 256 opacity map: a checker of 16-texel squares (0 / 255) with noise:
+    a fifth of the texels random bytes."""
+    rng = np.random.default_rng(seed)
+    j, i = np.meshgrid(np.arange(256), np.arange(256), indexing="ij")
+    tex = np.where(((i // 16 + j // 16) % 2) == 0, 255, 0)
+    tex = np.where(rng.random((256, 256)) < 0.2, rng.integers(0, 256, (256, 256)), tex).astype(np.uint8)
+    return [Material(flags=N.PBR_MAT_ALPHA_TEST, tex=(-1, -1, -1, -1, -1, 0)) for _ in range(n)], [tex]
+
+
+def timed_stages(ctx, draws, view, attrs, depth, steps, clip=False, alpha=False):
     """Per-stage medians of `steps` timed calls (each synchronises; the clock ramp is the untimed loop before)."""
     argtypes = [ctypes.c_void_p, ctypes.POINTER(N.DrawDesc), ctypes.c_int32, ctypes.POINTER(N.RasterView),
                 ctypes.POINTER(N.RasterTargets), ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
-    if clip:
+    kw = {**({"clip_near": True} if clip else {}), **({"alpha_test": True} if alpha else {})}
+    if clip or alpha:
         timed = ctx.lib.pbr_debug_rasterize_flags_timed
         timed.argtypes = argtypes[:5] + [ctypes.c_uint32] + argtypes[5:]
+        flags = (N.PBR_RASTER_CLIP_NEAR if clip else 0) | (N.PBR_RASTER_ALPHA_TEST if alpha else 0)
 
         def fn(h, c_draws, n, v, t, stream, ms):
-            return timed(h, c_draws, n, v, t, N.PBR_RASTER_CLIP_NEAR, stream, ms)
+            return timed(h, c_draws, n, v, t, flags, stream, ms)
     else:
         timed = fn = ctx.lib.pbr_debug_rasterize_timed
         timed.argtypes = argtypes
@@ -123,7 +139,7 @@ def timed_stages(ctx, draws, view, attrs, depth, steps, clip=False):
     rows = []
     t0 = time.perf_counter()
     while time.perf_counter() - t0 < 0.2:  # clock ramp
-        ctx.rasterize(draws, view, out=(attrs, depth), **({"clip_near": True} if clip else {}))
+        ctx.rasterize(draws, view, out=(attrs, depth), **kw)
     for _ in range(steps):
         N.check(fn(ctx.handle, c_draws, len(draws), ctypes.byref(v), ctypes.byref(t), stream, ms),
                 "pbr_debug_rasterize_timed", ctx.handle)
@@ -160,15 +176,18 @@ def main():
         lines.append(line)
 
     can_clip = hasattr(N.lib(), "pbr_rasterize_flags")
+    can_alpha = hasattr(N.lib(), "pbr_last_raster_alpha_stats")
     emit({"tool": "raster_bench", "width": W, "height": H, "sources_sha": info["sources_sha"],
           "checkout_sha": N.kernel_sources_sha(), "library": os.path.relpath(info["path"], ROOT),
-          "has_rasterize_flags": can_clip,
+          "has_rasterize_flags": can_clip, "has_alpha_test": can_alpha,
           "device": torch.cuda.get_device_name(0), "steps": a.steps, "resolve_bytes_per_pixel": BYTES_WRITTEN})
     cfg = S.REFERENCE_SCENE.with_size(W, H).with_camera(*S.OVERVIEW_CAMERA)
     ref_meshes, ref_draws = S.reference_scene_draws(a.slices, a.stacks)
     scenes = [("reference", ref_meshes, ref_draws, S.reference_scene_view(cfg)),
               ("stress",) + stress_scene(W, H, a.stress_triangles),
               ("walkthrough",) + walkthrough_scene(W, H, a.slices, a.stacks)]
+    if can_alpha:
+        scenes.append(("cutout", ref_meshes, ref_draws, S.reference_scene_view(cfg)))
     attrs = Attributes(torch.empty((14, H, W), dtype=torch.float32, device=dev),
                        torch.empty((H, W), dtype=torch.int16, device=dev))
     depth = torch.empty((H, W), dtype=torch.float32, device=dev)
@@ -180,21 +199,27 @@ def main():
         emit(c)
         for name, meshes, draws, view in scenes:
             ctx.set_meshes(meshes)
-            for clip in (False, True) if can_clip else (False,):
-                kw = {"clip_near": True} if clip else {}
+            if can_alpha:  # cutout: every sphere tested; the other scenes: a table without a tested material
+                ctx.set_materials(*(cutout_materials(len(draws)) if name == "cutout" else ([Material()] * 64, [])))
+            legs = [(False, False)] + ([(True, False)] if can_clip and name != "cutout" else [])
+            legs += [(False, True)] if can_alpha else []
+            for clip, alpha in legs:
+                kw = {**({"clip_near": True} if clip else {}), **({"alpha_test": True} if alpha else {})}
                 ctx.rasterize(draws, view, out=(attrs, depth), **kw)
                 stats = ctx.raster_stats()
                 if clip:
                     stats.update(ctx.raster_clip_stats())
+                if alpha:
+                    stats.update(ctx.raster_alpha_stats())
                 covered = int((attrs.material != -1).sum().item())
-                emit({"scene": name, "clip": clip, "stats": stats, "covered_pixels": covered,
+                emit({"scene": name, "clip": clip, "alpha": alpha, "stats": stats, "covered_pixels": covered,
                       "vertices": int(sum(m.vertices.shape[0] for m in meshes)), "draws": len(draws)})
-                st = timed_stages(ctx, draws, view, attrs, depth, a.steps, clip)
-                st.update(leg="a_stages_ms", scene=name, clip=clip, coverage_ms=st["setup_small"] + st["large"],
-                          resolve_over_copy=st["resolve"] / c["median_ms"])
+                st = timed_stages(ctx, draws, view, attrs, depth, a.steps, clip, alpha)
+                st.update(leg="a_stages_ms", scene=name, clip=clip, alpha=alpha,
+                          coverage_ms=st["setup_small"] + st["large"], resolve_over_copy=st["resolve"] / c["median_ms"])
                 emit(st)
                 whole = event_ms(lambda: ctx.rasterize(draws, view, out=(attrs, depth), **kw), a.steps)
-                whole.update(leg="b_whole_call", scene=name, clip=clip)
+                whole.update(leg="b_whole_call", scene=name, clip=clip, alpha=alpha)
                 emit(whole)
         host = []
         for _ in range(3):
