@@ -471,6 +471,72 @@ typedef struct pbr_raster_alpha_stats {
  * zeros after a call without PBR_RASTER_ALPHA_TEST and when the context has not rasterised on that stream. */
 int pbr_last_raster_alpha_stats(pbr_context* ctx, pbr_raster_alpha_stats* out, void* stream);
 
+/* ---- The transparent layer: ordered peel and blend (RenderLayer::Transparent, PBRApp.cpp:313-316, 829-844) -------
+ * The transparent PSO is the opaque one with CULL_MODE_NONE and blending: depth stays LESS with writes on, the pixel
+ * shader stays opaquePS (no alpha test, output alpha g_Opacity). At one pixel the fragments of the transparent draws
+ * arrive in primitive order; one with z below the depth buffer is blended over the colour and becomes the depth, every
+ * other is dropped: the blended fragments are the strict running minima of z in primitive order. pbr_rasterize_layer
+ * extracts that sequence one fragment per pixel per call: layer k is, per pixel, the fragment
+ * with the smallest primitive ordinal among those with ordinal >= floor and z < depth_in; the call writes its
+ * attributes, its z as the new depth and its ordinal + 1 as the next floor. Each layer goes through
+ * pbr_resolve_materials and a shading call unchanged and is blended over the frame by pbr_blend_layer. Additive:
+ * PBR_ABI_VERSION stays 9, detect by the symbol pbr_rasterize_layer. */
+typedef struct pbr_raster_layer {
+    const float* depth_in;   /* DEVICE, required: the depth before this layer (the opaque and alpha-tested layers' depth
+                              * plane for the first layer, 1 where they drew nothing); the targets' row stride and band */
+    const uint32_t* prim_in; /* DEVICE: the floor plane the previous layer wrote; NULL = 0 everywhere (the first layer) */
+    uint32_t* prim_out;      /* DEVICE, required: the floor for the next layer */
+} pbr_raster_layer;
+
+/* One layer. Arguments as pbr_rasterize_flags, plus `layer`; targets->depth is required. targets->depth may alias
+ * layer->depth_in and prim_out may alias prim_in: the coverage kernels only read the inputs, and the per-pixel resolve,
+ * which runs after them in stream order, reads and writes only its own pixel. A fragment (coverage passed, 0 <= z < 1,
+ * as for pbr_rasterize) is eligible iff its ordinal >= floor(x, y) and z < depth_in(x, y) (a NaN depth_in: never). A
+ * pixel with an eligible fragment gets the attributes and material of the one with the smallest ordinal, its z in the
+ * depth plane and its ordinal + 1 in prim_out. A pixel without one gets the background planes and PBR_MATERIAL_NONE (so
+ * the resolve gives it coverage 0), depth_in's value passed through in the depth plane, and 0xFFFFFFFF in prim_out:
+ * no later layer has an eligible fragment there. After the last layer the depth plane holds, bit for bit, what the
+ * depth buffer holds after the reference's transparent pass. The ordinals are the call's own -- draw order, then
+ * index order; the pieces of a clipped triangle share theirs -- so every layer of a sequence must pass the same draw
+ * list. `flags`: PBR_RASTER_CLIP_NEAR is accepted; PBR_RASTER_ALPHA_TEST is refused with PBR_ERR_INVALID_ARGUMENT (the
+ * transparent PSO runs no alpha test), as are unknown bits and bit 1. PBR_ERR_INVALID_ARGUMENT also for a null `layer`,
+ * depth_in, prim_out or targets->depth, or one of the planes not 4-byte aligned. pbr_raster_stats keeps its meanings:
+ * `fragments` counts coverage passed and 0 <= z < 1, eligible or not. */
+int pbr_rasterize_layer(pbr_context* ctx, const pbr_draw* draws, int32_t n_draws, const pbr_raster_view* view,
+                        const pbr_raster_targets* targets, uint32_t flags, const pbr_raster_layer* layer, void* stream);
+
+typedef struct pbr_raster_layer_stats {
+    int64_t layer_fragments; /* eligible fragments: the visibility updates issued. 0 = the layer is empty: stop */
+} pbr_raster_layer_stats;
+
+/* The layer counter of the last rasterisation on `stream` (synchronises it, like pbr_last_raster_stats); zeros after
+ * a call other than pbr_rasterize_layer and when the context has not rasterised on that stream. */
+int pbr_last_raster_layer_stats(pbr_context* ctx, pbr_raster_layer_stats* out, void* stream);
+
+/* A shaded layer, DEVICE memory: its colour, its alpha and where it has fragments. */
+typedef struct pbr_blend_source {
+    const float* src;            /* RGBA32F, 4-byte aligned (16-byte aligned: one access per pixel); .a is not read */
+    int64_t src_row_stride;      /* pixels, >= width */
+    const float* alpha;          /* the opacity plane pbr_resolve_materials wrote (without an opacity map: the
+                                  * material's `opacity`, g_Opacity, which opaquePS outputs as alpha) */
+    int64_t alpha_row_stride;    /* elements, >= width */
+    const uint8_t* coverage;     /* the coverage plane pbr_resolve_materials wrote for the layer */
+    int64_t coverage_row_stride; /* bytes, >= width */
+} pbr_blend_source;
+
+/* The output-merger blend of the transparent PSO (PBRApp.cpp:831-842: colour SRC_ALPHA / INV_SRC_ALPHA, alpha
+ * ONE / ZERO, both op ADD) of `source` over `dst` (out, out_row_stride and format are used; RGBA32F `out` may be only
+ * 4-byte aligned here), width x height pixels, asynchronously on `stream`. Per pixel with nonzero coverage, with a the
+ * alpha value and s the source colour: RGBA32F: out.c = (s.c * a) + (d.c * (1.0f - a)), each operation rounded once,
+ * out.a = a. RGBA8_UNORM: d.c = (float)byte / 255.0f, s.c and a first clamped to [0, 1] with NaN -> 0 (the fixed-point
+ * render-target rule), the same expression, all four results encoded with the FLOAT -> UNORM rule of pbr_output_format.
+ * A pixel with coverage 0 is neither read nor written in `dst`. Not a shading pass: the pass statistics stay.
+ * Departure from the reference: this blends over the finished opaque + sky frame. The reference draws its sky after
+ * the transparent layer, so a transparent fragment over empty background blends there with the grey clear colour and
+ * then hides the sky -- an artefact of its draw order that is not reproduced. */
+int pbr_blend_layer(pbr_context* ctx, const pbr_blend_source* source, const pbr_frame_desc* dst, int32_t width,
+                    int32_t height, void* stream);
+
 /* ---- Host G-buffer fill (replaces the VS + rasteriser front-end, Default.hlsl:22-45) ---------- */
 
 typedef enum pbr_scene_kind {

@@ -388,6 +388,30 @@ class ShadingContext {
     // discarded before the depth update where the opacity texture says so; needs SetMaterials).
     void Rasterize(const std::vector<pbr_draw>& draws, const pbr_raster_view& view, DeviceAttributes& attrs,
                    float* depth = nullptr, hipStream_t stream = nullptr, uint32_t flags = 0) {
+        Rasterize(draws, view, attrs, depth, stream, flags, nullptr);
+    }
+    // One layer of the transparent pass (pbr_rasterize_layer): per pixel the fragment with the
+    // smallest primitive ordinal among those at or past layer.prim_in's floor (NULL: 0) and nearer than layer.depth_in;
+    // `depth` (required; it may be layer.depth_in) receives its z, layer.prim_out the next floor. Every layer of a
+    // sequence passes the same `draws`. `flags`: 0 or PBR_RASTER_CLIP_NEAR.
+    void RasterizeLayer(const std::vector<pbr_draw>& draws, const pbr_raster_view& view, DeviceAttributes& attrs,
+                        float* depth, const pbr_raster_layer& layer, hipStream_t stream = nullptr, uint32_t flags = 0) {
+        Rasterize(draws, view, attrs, depth, stream, flags, &layer);
+    }
+    pbr_raster_layer_stats LastRasterLayerStats(hipStream_t stream = nullptr) {
+        pbr_raster_layer_stats s;
+        Check(pbr_last_raster_layer_stats(ctx_, &s, stream), "pbr_last_raster_layer_stats");
+        return s;
+    }
+    // The transparent PSO's blend of a shaded layer over `dst` where the layer has coverage (pbr_blend_layer).
+    void BlendLayer(const pbr_blend_source& source, const pbr_frame_desc& dst, int32_t width, int32_t height,
+                    hipStream_t stream = nullptr) {
+        Check(pbr_blend_layer(ctx_, &source, &dst, width, height, stream), "pbr_blend_layer");
+    }
+
+  private:
+    void Rasterize(const std::vector<pbr_draw>& draws, const pbr_raster_view& view, DeviceAttributes& attrs, float* depth,
+                   hipStream_t stream, uint32_t flags, const pbr_raster_layer* layer) {
         const pbr_attributes_soa band = attrs.Band(view.row_begin, view.row_end);
         pbr_raster_targets t;
         std::memset(&t, 0, sizeof t);
@@ -402,12 +426,17 @@ class ShadingContext {
         t.material = const_cast<uint16_t*>(band.material);
         t.depth = depth;
         t.row_stride = band.row_stride;
-        if (flags == 0)
+        if (layer)
+            Check(pbr_rasterize_layer(ctx_, draws.data(), static_cast<int32_t>(draws.size()), &view, &t, flags, layer,
+                                      stream), "pbr_rasterize_layer");
+        else if (flags == 0)
             Check(pbr_rasterize(ctx_, draws.data(), static_cast<int32_t>(draws.size()), &view, &t, stream), "pbr_rasterize");
         else
             Check(pbr_rasterize_flags(ctx_, draws.data(), static_cast<int32_t>(draws.size()), &view, &t, flags, stream),
                   "pbr_rasterize_flags");
     }
+
+  public:
     pbr_raster_clip_stats LastRasterClipStats(hipStream_t stream = nullptr) {
         pbr_raster_clip_stats s;
         Check(pbr_last_raster_clip_stats(ctx_, &s, stream), "pbr_last_raster_clip_stats");

@@ -267,6 +267,33 @@ class RasterAlphaStats(ctypes.Structure):
     ]
 
 
+class RasterLayer(ctypes.Structure):
+    """pbr_raster_layer: the planes of one layer of the transparent pass (pbr_rasterize_layer)."""
+    _fields_ = [
+        ("depth_in", ctypes.c_void_p),
+        ("prim_in", ctypes.c_void_p),
+        ("prim_out", ctypes.c_void_p),
+    ]
+
+
+class RasterLayerStats(ctypes.Structure):
+    _fields_ = [
+        ("layer_fragments", ctypes.c_int64),
+    ]
+
+
+class BlendSource(ctypes.Structure):
+    """pbr_blend_source: a shaded layer for pbr_blend_layer."""
+    _fields_ = [
+        ("src", ctypes.c_void_p),
+        ("src_row_stride", ctypes.c_int64),
+        ("alpha", ctypes.c_void_p),
+        ("alpha_row_stride", ctypes.c_int64),
+        ("coverage", ctypes.c_void_p),
+        ("coverage_row_stride", ctypes.c_int64),
+    ]
+
+
 class PassStats(ctypes.Structure):
     """pbr_pass_stats: statistics of the last shading pass."""
     _fields_ = [
@@ -328,6 +355,13 @@ SIGNATURES = {
     "pbr_last_raster_clip_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(RasterClipStats), ctypes.c_void_p]),
     "pbr_last_raster_alpha_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(RasterAlphaStats),
                                                    ctypes.c_void_p]),
+    "pbr_rasterize_layer": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(DrawDesc), ctypes.c_int32,
+                                           ctypes.POINTER(RasterView), ctypes.POINTER(RasterTargets), ctypes.c_uint32,
+                                           ctypes.POINTER(RasterLayer), ctypes.c_void_p]),
+    "pbr_last_raster_layer_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(RasterLayerStats),
+                                                   ctypes.c_void_p]),
+    "pbr_blend_layer": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(BlendSource), ctypes.POINTER(FrameDesc),
+                                       ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),
     "pbr_attributes_fill": (ctypes.c_int64, [ctypes.POINTER(SceneDesc), ctypes.c_int32, ctypes.c_int32,
                                              ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.c_int64,
                                              ctypes.c_int32]),

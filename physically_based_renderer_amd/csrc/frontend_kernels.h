@@ -70,10 +70,11 @@ struct RasterVertex {
     uint32_t pad;
 };
 // Counters of a call, unsigned 64-bit words in device memory (pbr_raster_stats, pbr_raster_clip_stats,
-// pbr_raster_alpha_stats; kRasterLarge: the large-triangle list's length). The first eight keep their slots.
+// pbr_raster_alpha_stats, pbr_raster_layer_stats; kRasterLarge: the large-triangle list's length). The first ten keep
+// their slots.
 enum RasterCounter { kRasterLarge = 0, kRasterCulled, kRasterZeroArea, kRasterNear, kRasterGuard, kRasterFragments,
                      kRasterClipped, kRasterClipPieces, kRasterAlphaTested, kRasterAlphaDiscarded,
-                     kRasterCounters = 10 };
+                     kRasterLayerFragments, kRasterCounters = 11 };
 
 struct RasterArgs {
     const float* vertices;    // the mesh set: 14 floats per vertex
@@ -106,15 +107,39 @@ struct RasterArgs {
     const uint32_t* texels;    // every texture, RGBA8
     int64_t n_texels;
     bool alpha_test;   // some draw's material has kMatAlphaTest: setup and large launch their ALPHA instantiations
+    // Appended for pbr_rasterize_layer (step 7a), read by the PEEL instantiations only. The three planes have the
+    // targets' row stride and point at row `row_begin`; depth_in may be `depth`, prim_in may be prim_out.
+    const float* depth_in;     // d_(k-1): a fragment is eligible only with z < depth_in
+    const uint32_t* prim_in;   // the floor f_(k-1): ... and with an ordinal >= it; nullptr: 0 everywhere
+    uint32_t* prim_out;        // f_k: the winner's ordinal + 1, 0xFFFFFFFF without a winner
+    bool peel;         // a layer call: setup, large and resolve launch their PEEL instantiations (never with alpha_test)
 };
 // The stages of pbr_rasterize, each one launch (none when it has nothing to do): the vertex transform, the triangle
 // setup with the small triangles' coverage, the large triangles' coverage, the per-pixel resolve. With a.clip_near
 // each launches its near-clipping instantiation; with a.alpha_test the setup and the
-// large-triangle stage launch their alpha-testing instantiations (step 6a).
+// large-triangle stage launch their alpha-testing instantiations (step 6a); with a.peel the setup, the large-triangle
+// stage and the resolve launch their layer instantiations (step 7a).
 hipError_t launch_raster_vertices(const RasterArgs& a, hipStream_t stream);
 hipError_t launch_raster_setup(const RasterArgs& a, hipStream_t stream);
 hipError_t launch_raster_large(const RasterArgs& a, hipStream_t stream);
 hipError_t launch_raster_resolve(const RasterArgs& a, hipStream_t stream);
+
+// ---- Layer blend (blend_layer.h; pbr_blend_layer) -------------------------------------------------
+// The output-merger blend of the transparent PSO (PBRApp.cpp:831-842): SRC_ALPHA / INV_SRC_ALPHA on colour, ONE / ZERO
+// on alpha, of a shaded layer over a frame, on the pixels the layer covers.
+struct BlendArgs {
+    const float* src;         // RGBA32F, 4 floats per pixel
+    const float* alpha;       // fp32 plane: the layer's opacity
+    const uint8_t* coverage;  // the layer's coverage: 0 = the destination pixel is neither read nor written
+    void* out;                // RGBA32F or RGBA8
+    int64_t src_stride, out_stride;  // pixels
+    int64_t alpha_stride, cov_stride;  // elements
+    int width, height;
+    int format;  // kBlendRgba32f / kBlendRgba8
+    bool vec;    // src and (RGBA32F) out 16-byte aligned: one 16-byte access per pixel
+};
+constexpr int kBlendRgba32f = 0, kBlendRgba8 = 1;
+hipError_t launch_blend_layer(const BlendArgs& a, hipStream_t stream);
 
 // PBR_DEBUG_BOUNDS builds only (pbr_debug_bounds.h): point this unit's kernels at the device's bounds-flag buffer.
 hipError_t debug_bounds_publish_frontend(uint32_t* buf);

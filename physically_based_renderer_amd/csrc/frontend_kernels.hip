@@ -1,6 +1,6 @@
 // frontend_kernels.hip -- gfx950 kernels of the front end, which turns meshes and materials into the G-buffer the
 // shading kernels read: the rasteriser (raster.h; pbr_rasterize) and the material resolve (material_resolve.h;
-// pbr_resolve_materials). A unit of its own, so a front-end change never recompiles the shading kernels. The Makefile
+// pbr_resolve_materials); and the blend of a shaded transparent layer over the frame (blend_layer.h; pbr_blend_layer). A unit of its own, so a front-end change never recompiles the shading kernels. The Makefile
 // gives it the flags these kernels were first built and measured under: the canonical fp32 flags and the max-ILP
 // machine scheduler.
 #include <hip/hip_runtime.h>
@@ -11,6 +11,7 @@
 #include "frontend_kernels.h"
 #include "material_resolve.h"
 #include "raster.h"
+#include "blend_layer.h"
 
 namespace pbr {
 

@@ -228,13 +228,20 @@ int pbr_set_meshes(pbr_context* ctx, const pbr_mesh_desc* meshes, int32_t n_mesh
 
 namespace {
 
-// pbr_rasterize (flags 0) and pbr_rasterize_flags. `marks` (development, pbr_debug_rasterize_timed): six events
+// pbr_rasterize (flags 0), pbr_rasterize_flags and, with `layer`, pbr_rasterize_layer. `marks` (development, pbr_debug_rasterize_timed): six events
 // recorded around the five stages -- clears and table upload, vertex transform, setup with the small triangles'
 // coverage, large triangles, resolve.
 int rasterize_impl(pbr_context* ctx, const pbr_draw* draws, int32_t n_draws, const pbr_raster_view* view,
-                   const pbr_raster_targets* tg, uint32_t flags, void* stream, hipEvent_t* marks) {
+                   const pbr_raster_targets* tg, uint32_t flags, void* stream, hipEvent_t* marks,
+                   const pbr_raster_layer* layer = nullptr) {
     if (!ctx || !view || !tg || n_draws < 0 || (n_draws > 0 && !draws)) return PBR_ERR_INVALID_ARGUMENT;
     if (flags & ~(uint32_t)(PBR_RASTER_CLIP_NEAR | PBR_RASTER_ALPHA_TEST)) return PBR_ERR_INVALID_ARGUMENT;
+    if (layer) {  // the transparent PSO runs no alpha test; the layer's planes and the depth plane are required
+        if (flags & PBR_RASTER_ALPHA_TEST) return PBR_ERR_INVALID_ARGUMENT;
+        if (!layer->depth_in || !layer->prim_out || !tg->depth) return PBR_ERR_INVALID_ARGUMENT;
+        if (!aligned(layer->depth_in, 4) || !aligned(layer->prim_in, 4) || !aligned(layer->prim_out, 4))
+            return PBR_ERR_INVALID_ARGUMENT;
+    }
     const bool clip_near = (flags & PBR_RASTER_CLIP_NEAR) != 0;
     if (view->width < 0 || view->height < 0 || view->width > kRasterMaxSide || view->height > kRasterMaxSide)
         return PBR_ERR_INVALID_ARGUMENT;
@@ -255,6 +262,13 @@ int rasterize_impl(pbr_context* ctx, const pbr_draw* draws, int32_t n_draws, con
     a.material = tg->material;
     a.depth = tg->depth;
     a.vec = a.vec && aligned(tg->material, 4) && aligned(tg->depth, 8);
+    if (layer) {
+        a.peel = true;
+        a.depth_in = layer->depth_in;
+        a.prim_in = layer->prim_in;
+        a.prim_out = layer->prim_out;
+        a.vec = a.vec && aligned(layer->prim_out, 8);
+    }
     a.stride = tg->row_stride;
     a.width = view->width;
     a.height = view->height;
@@ -423,6 +437,12 @@ int pbr_rasterize_flags(pbr_context* ctx, const pbr_draw* draws, int32_t n_draws
     return rasterize_impl(ctx, draws, n_draws, view, targets, flags, stream, nullptr);
 }
 
+int pbr_rasterize_layer(pbr_context* ctx, const pbr_draw* draws, int32_t n_draws, const pbr_raster_view* view,
+                        const pbr_raster_targets* targets, uint32_t flags, const pbr_raster_layer* layer, void* stream) {
+    if (!layer) return PBR_ERR_INVALID_ARGUMENT;
+    return rasterize_impl(ctx, draws, n_draws, view, targets, flags, stream, nullptr, layer);
+}
+
 }  // extern "C"
 
 // The counters of the last rasterisation on `stream` into h (synchronises it) and its triangle count; *ran false (and
@@ -488,6 +508,49 @@ int pbr_last_raster_alpha_stats(pbr_context* ctx, pbr_raster_alpha_stats* out, v
     return PBR_OK;
 }
 
+int pbr_last_raster_layer_stats(pbr_context* ctx, pbr_raster_layer_stats* out, void* stream) {
+    if (!ctx || !out) return PBR_ERR_INVALID_ARGUMENT;
+    *out = pbr_raster_layer_stats{};
+    unsigned long long h[pbr::kRasterCounters] = {};  // every call clears them: zeros unless the call was a layer's
+    int64_t triangles = 0;
+    bool ran = false;
+    if (const int rc = read_raster_counters(ctx, stream, h, &triangles, &ran, "pbr_last_raster_layer_stats")) return rc;
+    out->layer_fragments = (int64_t)h[pbr::kRasterLayerFragments];
+    return PBR_OK;
+}
+
+// The transparent PSO's output-merger blend of a shaded layer over the frame (blend_layer.h).
+int pbr_blend_layer(pbr_context* ctx, const pbr_blend_source* src, const pbr_frame_desc* dst, int32_t width,
+                    int32_t height, void* stream) {
+    if (!ctx || !src || !dst || width < 0 || height < 0) return PBR_ERR_INVALID_ARGUMENT;
+    if (dst->format != PBR_OUTPUT_RGBA32F && dst->format != PBR_OUTPUT_RGBA8_UNORM) return PBR_ERR_INVALID_ARGUMENT;
+    if (!src->src || !src->alpha || !src->coverage || !dst->out) return PBR_ERR_INVALID_ARGUMENT;
+    if (!aligned(src->src, 4) || !aligned(src->alpha, 4) || !aligned(dst->out, 4)) return PBR_ERR_INVALID_ARGUMENT;
+    if (src->src_row_stride < width || src->alpha_row_stride < width || src->coverage_row_stride < width ||
+        dst->out_row_stride < width)
+        return PBR_ERR_INVALID_ARGUMENT;
+    Entry en(ctx);
+    if (width == 0 || height == 0) return PBR_OK;  // an empty frame: nothing is read or written
+    pbr::BlendArgs a{};
+    a.src = src->src;
+    a.alpha = src->alpha;
+    a.coverage = src->coverage;
+    a.out = dst->out;
+    a.src_stride = src->src_row_stride;
+    a.alpha_stride = src->alpha_row_stride;
+    a.cov_stride = src->coverage_row_stride;
+    a.out_stride = dst->out_row_stride;
+    a.width = width;
+    a.height = height;
+    a.format = dst->format == PBR_OUTPUT_RGBA8_UNORM ? pbr::kBlendRgba8 : pbr::kBlendRgba32f;
+    a.vec = aligned(src->src, 16) && (a.format == pbr::kBlendRgba8 || aligned(dst->out, 16));
+    // Not a shading pass and a reader of no context resource: the stream's statistics record, its kernel name and the
+    // ordering events stay as they are.
+    if (const int rc = en.device(stream)) return rc;
+    const hipError_t e = pbr::launch_blend_layer(a, en.s);
+    return e == hipSuccess ? PBR_OK : fail_hip(ctx, e, "blend_layer_kernel launch", PBR_ERR_LAUNCH);
+}
+
 }  // extern "C"
 
 // Development (tools/raster_bench.py; not in the public header): one pbr_rasterize_flags with HIP events between its
@@ -503,6 +566,28 @@ extern "C" int pbr_debug_rasterize_flags_timed(pbr_context* ctx, const pbr_draw*
     hipError_t e = hipSuccess;
     for (int i = 0; i < 6 && e == hipSuccess; ++i) e = hipEventCreate(&ev[i]);
     int rc = e == hipSuccess ? rasterize_impl(ctx, draws, n_draws, view, targets, flags, stream, ev) : PBR_ERR_HIP;
+    if (rc == PBR_OK && hipStreamSynchronize(static_cast<hipStream_t>(stream)) != hipSuccess) rc = PBR_ERR_HIP;
+    for (int i = 0; i < 5; ++i) {
+        ms5[i] = 0.0f;
+        if (rc == PBR_OK && hipEventElapsedTime(&ms5[i], ev[i], ev[i + 1]) != hipSuccess) rc = PBR_ERR_HIP;
+    }
+    for (hipEvent_t x : ev)
+        if (x) (void)hipEventDestroy(x);
+    return rc;
+}
+
+// The same for pbr_rasterize_layer.
+extern "C" int pbr_debug_rasterize_layer_timed(pbr_context* ctx, const pbr_draw* draws, int32_t n_draws,
+                                               const pbr_raster_view* view, const pbr_raster_targets* targets,
+                                               uint32_t flags, const pbr_raster_layer* layer, void* stream,
+                                               float* ms5) {
+    if (!ctx || !ms5 || !layer) return PBR_ERR_INVALID_ARGUMENT;
+    DeviceGuard g(ctx->device);
+    if (!g.ok) return PBR_ERR_NO_DEVICE;
+    hipEvent_t ev[6] = {};
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < 6 && e == hipSuccess; ++i) e = hipEventCreate(&ev[i]);
+    int rc = e == hipSuccess ? rasterize_impl(ctx, draws, n_draws, view, targets, flags, stream, ev, layer) : PBR_ERR_HIP;
     if (rc == PBR_OK && hipStreamSynchronize(static_cast<hipStream_t>(stream)) != hipSuccess) rc = PBR_ERR_HIP;
     for (int i = 0; i < 5; ++i) {
         ms5[i] = 0.0f;

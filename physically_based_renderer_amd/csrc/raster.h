@@ -37,6 +37,15 @@
 // for instruction. A fragment of a tested draw interpolates its TexCoord with the resolve's operations, fetches the
 // material resolve's point-wrap tap of the opacity texture and, with opacity - 0.1 < 0, issues no visibility update.
 // The vertex and resolve kernels do not change: the winner is still the key's triangle.
+//
+// A layer of the transparent pass (pbr_rasterize_layer; RenderLayer::Transparent,
+// PBRApp.cpp:313-316: depth LESS with writes on, blending) is a further instantiation (template parameter PEEL) of the
+// setup kernels, the large-triangle kernel and the resolve, launched by a layer call only and never with ALPHA; the
+// PEEL = false instantiations are the kernels of the other calls, instruction for instruction. A fragment is eligible
+// iff its ordinal is at least the pixel's floor and its z is below the incoming depth; the visibility word is
+// (ordinal << 32) | bits(z), so the atomicMin keeps the earliest eligible fragment in submission order -- the next
+// fragment the D3D depth test would accept. The resolve writes that fragment's attributes, its z as the new depth and
+// its ordinal + 1 as the next floor; a pixel without one keeps the incoming depth and gets the floor 0xFFFFFFFF.
 #pragma once
 
 #include "pbr_device_math.h"
@@ -312,6 +321,41 @@ struct FragCounts {
     }
 };
 
+// ---- Layer peel (step 7a; the PEEL instantiations; pbr_rasterize_layer) ----
+// raster_pixel with the eligibility test between the depth range and the visibility update, and the key's halves
+// exchanged: (ordinal << 32) | bits(z), so the smallest eligible ordinal wins. A fragment is eligible iff
+// z < depth_in (a NaN depth_in: never) and prim >= the floor. depth_in and prim_in are read only after coverage and
+// the depth range passed; both only read here (the resolve, later in stream order, is what may overwrite them).
+// Bit 0: a fragment exists; bit 1: it issued a visibility update.
+constexpr uint32_t kFragUpdate = 2u;
+__device__ __forceinline__ uint32_t raster_pixel_peel(const RasterArgs& a, const Tri& s, const Edges& e,
+                                                      const float z[3], uint32_t prim, int x, int y) {
+    const long long E[3] = {edge_at(e, 0, x, y), edge_at(e, 1, x, y), edge_at(e, 2, x, y)};
+    if (!covered(e, E)) return 0u;
+    float l[3];
+    barycentrics(E, s.A, l);
+    const float zf = interpolate_z(l, z);
+    if (!(zf >= 0.0f && zf < 1.0f)) return 0u;
+    const int band_h = a.row_end - a.row_begin;
+    const int64_t i = PBR_BOUNDS_PIXEL((int64_t)(y - a.row_begin) * a.stride + x, a.width, band_h, a.stride, 1,
+                                       kBoundsRaster);
+    if (!(zf < a.depth_in[i])) return kFragment;
+    if (a.prim_in != nullptr && prim < a.prim_in[i]) return kFragment;
+    const unsigned long long key = ((unsigned long long)prim << 32) | (unsigned long long)__float_as_uint(zf);
+    [[maybe_unused]] const int64_t n_vis = (int64_t)band_h * a.width;
+    atomicMin(a.vis + PBR_BOUNDS((int64_t)(y - a.row_begin) * a.width + x, n_vis, kBoundsRaster), key);
+    return kFragment | kFragUpdate;
+}
+
+// A lane's (or workgroup's) counts of a layer call: the fragments that exist and the visibility updates issued.
+struct PeelCounts {
+    uint32_t frags = 0, updates = 0;
+    __device__ __forceinline__ void add(uint32_t r) {
+        frags += r & 1u;
+        updates += r >> 1;
+    }
+};
+
 // ---- Near-plane clipping (step 2a) ----
 // A piece of a clipped triangle after setup: s as for a triangle, with s.rec[v] the submitted vertex that piece
 // vertex v is (recb[v] == s.rec[v]) or the inside end of the edge whose crossing with z = 0 it is (recb[v]: the outside
@@ -498,6 +542,14 @@ __device__ __forceinline__ void raster_small_alpha(const RasterArgs& a, const Tr
     for (int y = b.y0; y <= b.y1; ++y)
         for (int x = b.x0; x <= b.x1; ++x) n.add(raster_pixel_alpha(a, s, e, z, al, prim, x, y));
 }
+// The same for a layer call (step 7a).
+__device__ __forceinline__ void raster_small_peel(const RasterArgs& a, const Tri& s, const Box& b, const float z[3],
+                                                  uint32_t prim, PeelCounts& n) {
+    Edges e;
+    tri_edges(s, e);
+    for (int y = b.y0; y <= b.y1; ++y)
+        for (int x = b.x0; x <= b.x1; ++x) n.add(raster_pixel_peel(a, s, e, z, prim, x, y));
+}
 
 // Appends the wave's large triangles (or pieces: `piece` in the top bit of the block count) to the list: one atomic
 // per wave. Every lane of the wave calls it.
@@ -522,9 +574,11 @@ __device__ __forceinline__ void append_large(const RasterArgs& a, bool large, co
 
 // Stage 2: setup of every triangle, the statistics, the small triangles' coverage, the large list. ALPHA (a call with
 // PBR_RASTER_ALPHA_TEST some draw of which has a tested material): each lane has its own triangle, so the material
-// record is read per lane, and rw and TexCoord only by the lane of a small triangle of a tested draw.
-template <bool ALPHA>
+// record is read per lane, and rw and TexCoord only by the lane of a small triangle of a tested draw. PEEL (a layer
+// call, pbr_rasterize_layer; never with ALPHA): the small triangles' fragments take the eligibility test of step 7a.
+template <bool ALPHA, bool PEEL>
 __global__ __launch_bounds__(256) void raster_setup_kernel(const RasterArgs a) {
+    static_assert(!(ALPHA && PEEL), "a layer call runs no alpha test");
     using namespace raster;
     const uint32_t t = blockIdx.x * 256u + threadIdx.x;
     const bool valid = t < a.n_tris;
@@ -554,6 +608,15 @@ __global__ __launch_bounds__(256) void raster_setup_kernel(const RasterArgs a) {
         frags = n.frags;
         count_wave(a.counters + kRasterAlphaTested, n.tested);
         count_wave(a.counters + kRasterAlphaDiscarded, n.discarded);
+    } else if constexpr (PEEL) {
+        PeelCounts n;
+        if (small) {
+            float z[3];
+            load_z(a, s, z);
+            raster_small_peel(a, s, b, z, t, n);
+        }
+        frags = n.frags;
+        count_wave(a.counters + kRasterLayerFragments, n.updates);
     } else if (small) {
         Edges e;
         tri_edges(s, e);
@@ -583,9 +646,10 @@ __global__ __launch_bounds__(256) void raster_setup_kernel(const RasterArgs a) {
 // Stage 2 with near clipping: the lane of a clipped triangle walks its (at most two) pieces; each is counted,
 // rasterised or listed as a submitted triangle would be. Both rounds of the piece loop are taken by every lane, so the
 // wave-wide ballots and sums inside it see the whole wave. ALPHA: as in raster_setup_kernel; a piece takes the test with
-// its own rw and its new vertices' TexCoord.
-template <bool ALPHA>
+// its own rw and its new vertices' TexCoord. PEEL: as in raster_setup_kernel; the pieces of a triangle share its ordinal.
+template <bool ALPHA, bool PEEL>
 __global__ __launch_bounds__(256) void raster_setup_clip_kernel(const RasterArgs a) {
+    static_assert(!(ALPHA && PEEL), "a layer call runs no alpha test");
     using namespace raster;
     const uint32_t t = blockIdx.x * 256u + threadIdx.x;
     Tri src;
@@ -600,6 +664,7 @@ __global__ __launch_bounds__(256) void raster_setup_clip_kernel(const RasterArgs
     uint32_t culled = st == kTriCulled, zero = st == kTriZeroArea, near = st == kTriNear, guard = st == kTriGuard;
     uint32_t frags = 0;
     [[maybe_unused]] FragCounts n;
+    [[maybe_unused]] PeelCounts np;
     for (int p = 0; p < 2; ++p) {
         Piece P;
         Box b{0, -1, 0, -1};
@@ -628,6 +693,8 @@ __global__ __launch_bounds__(256) void raster_setup_clip_kernel(const RasterArgs
                         alpha_vertices(a, P.s, al);
                 }
                 raster_small_alpha(a, P.s, b, P.z, al, t, n);
+            } else if constexpr (PEEL) {
+                raster_small_peel(a, P.s, b, P.z, t, np);
             } else {
                 frags += raster_small(a, P.s, b, P.z, t);
             }
@@ -635,6 +702,7 @@ __global__ __launch_bounds__(256) void raster_setup_clip_kernel(const RasterArgs
         append_large(a, large, b, t, (uint32_t)p, a.n_large);
     }
     if constexpr (ALPHA) frags = n.frags;
+    if constexpr (PEEL) frags = np.frags;
     count_wave(a.counters + kRasterCulled, culled);
     count_wave(a.counters + kRasterZeroArea, zero);
     count_wave(a.counters + kRasterNear, near);
@@ -644,6 +712,7 @@ __global__ __launch_bounds__(256) void raster_setup_clip_kernel(const RasterArgs
         count_wave(a.counters + kRasterAlphaTested, n.tested);
         count_wave(a.counters + kRasterAlphaDiscarded, n.discarded);
     }
+    if constexpr (PEEL) count_wave(a.counters + kRasterLayerFragments, np.updates);
 }
 
 // Stage 3: the large triangles. blockIdx.x strides over the list, blockIdx.y over the triangle's 64 x 4 blocks; a wave
@@ -651,14 +720,18 @@ __global__ __launch_bounds__(256) void raster_setup_clip_kernel(const RasterArgs
 // triangle or, with the piece's number in the top bit of its block count, a piece of a clipped one.
 // ALPHA: the workgroup's triangle has one draw, so its material record and the "tested" decision are wave-uniform: the
 // record arrives by scalar loads and the test's branch is uniform; only the texel fetch is per lane.
-template <bool CLIP, bool ALPHA>
+// PEEL (never with ALPHA): a lane reads depth_in and the floor of its own pixel, after coverage and the depth range
+// passed; the lanes of a wave are adjacent in x, so these are coalesced 4-byte loads.
+template <bool CLIP, bool ALPHA, bool PEEL>
 __global__ __launch_bounds__(256) void raster_large_kernel(const RasterArgs a) {
+    static_assert(!(ALPHA && PEEL), "a layer call runs no alpha test");
     using namespace raster;
     const unsigned long long listed = a.counters[kRasterLarge];
     const uint32_t slots = CLIP ? (uint32_t)a.n_large : a.n_tris;
     const uint32_t n_large = listed < (unsigned long long)slots ? (uint32_t)listed : slots;
     uint32_t frags = 0;
     [[maybe_unused]] FragCounts n;
+    [[maybe_unused]] PeelCounts np;
     for (uint32_t i = blockIdx.x; i < n_large; i += gridDim.x) {
         const uint2 entry = a.large[PBR_BOUNDS((int64_t)i, (int64_t)slots, kBoundsRaster)];
         const uint32_t blocks = CLIP ? entry.y & 0x7FFFFFFFu : entry.y;
@@ -714,17 +787,21 @@ __global__ __launch_bounds__(256) void raster_large_kernel(const RasterArgs a) {
             const int x = X0 + (int)(threadIdx.x & 63u), y = Y0 + (int)(threadIdx.x >> 6);
             if constexpr (ALPHA) {
                 if (x <= X1 && y <= Y1) n.add(raster_pixel_alpha(a, s, e, z, al, t, x, y));
+            } else if constexpr (PEEL) {
+                if (x <= X1 && y <= Y1) np.add(raster_pixel_peel(a, s, e, z, t, x, y));
             } else {
                 if (x <= X1 && y <= Y1) frags += raster_pixel(a, s, e, z, t, x, y);
             }
         }
     }
     if constexpr (ALPHA) frags = n.frags;
+    if constexpr (PEEL) frags = np.frags;
     count_wave(a.counters + kRasterFragments, frags);
     if constexpr (ALPHA) {
         count_wave(a.counters + kRasterAlphaTested, n.tested);
         count_wave(a.counters + kRasterAlphaDiscarded, n.discarded);
     }
+    if constexpr (PEEL) count_wave(a.counters + kRasterLayerFragments, np.updates);
 }
 
 namespace raster {
@@ -796,12 +873,15 @@ __device__ __forceinline__ bool resolve_clipped(const RasterArgs& a, const Tri& 
     return false;
 }
 
-// One pixel of the band: the winner's attributes (step 8) or the background (step 9).
-template <bool CLIP>
+// One pixel of the band: the winner's attributes (step 8) or the background (step 9). PEEL: the visibility word of a
+// layer call holds the ordinal in its high half and the z bits in its low half; exchanged, it is the word the steps
+// below know (all ones stays all ones).
+template <bool CLIP, bool PEEL>
 __device__ __forceinline__ void resolve_pixel(const RasterArgs& a, int x, int y, float out[14], uint32_t& material,
                                               float& depth) {
     [[maybe_unused]] const int64_t n_vis = (int64_t)(a.row_end - a.row_begin) * a.width;
-    const unsigned long long key = a.vis[PBR_BOUNDS((int64_t)(y - a.row_begin) * a.width + x, n_vis, kBoundsRaster)];
+    unsigned long long key = a.vis[PBR_BOUNDS((int64_t)(y - a.row_begin) * a.width + x, n_vis, kBoundsRaster)];
+    if constexpr (PEEL) key = (key << 32) | (key >> 32);
     Tri s;
     if constexpr (CLIP) {
         uint32_t outside = 0;
@@ -837,11 +917,29 @@ __device__ __forceinline__ void resolve_pixel(const RasterArgs& a, int x, int y,
     material = a.draws[PBR_BOUNDS((int64_t)s.draw, (int64_t)a.n_draws, kBoundsRaster)].material;
 }
 
+// Step 7a's end at band pixel (x, yb), plane offset oi: with a winner (its depth is already the winner's z) the next
+// floor is its ordinal + 1; without one the depth is depth_in's value passed through and the floor 0xFFFFFFFF, which
+// no ordinal reaches.
+__device__ __forceinline__ void peel_pixel(const RasterArgs& a, int x, int yb, int64_t oi, float& depth,
+                                           uint32_t& floor) {
+    const int band_h = a.row_end - a.row_begin;
+    [[maybe_unused]] const int64_t n_vis = (int64_t)band_h * a.width;
+    const unsigned long long key = a.vis[PBR_BOUNDS((int64_t)yb * a.width + x, n_vis, kBoundsRaster)];
+    if (key != ~0ull) {
+        floor = (uint32_t)(key >> 32) + 1u;
+    } else {
+        depth = a.depth_in[PBR_BOUNDS_PIXEL(oi, a.width, band_h, a.stride, 1, kBoundsRaster)];
+        floor = 0xFFFFFFFFu;
+    }
+}
+
 }  // namespace raster
 
 // Stage 4: per pixel, the material resolve's tile: 256 threads over 64 x 8 pixels, a pixel pair per lane, 8-byte
-// plane stores when VEC.
-template <bool VEC, bool CLIP>
+// plane stores when VEC. PEEL (step 7a): a pixel without a winner keeps depth_in's value as its depth, and every
+// pixel writes its next floor to prim_out. A lane reads depth_in (which may be the depth plane) at its own pixels only,
+// before it stores them.
+template <bool VEC, bool CLIP, bool PEEL>
 __global__ __launch_bounds__(256) void raster_resolve_kernel(const RasterArgs a) {
     using namespace raster;
     const int band_h = a.row_end - a.row_begin;
@@ -850,15 +948,21 @@ __global__ __launch_bounds__(256) void raster_resolve_kernel(const RasterArgs a)
     const bool in0 = yb < band_h && x < a.width, in1 = yb < band_h && x + 1 < a.width;
     float v0[14], v1[14], z0 = 1.0f, z1 = 1.0f;
     uint32_t m0 = 0xFFFFu, m1 = 0xFFFFu;
-    if (in0) resolve_pixel<CLIP>(a, x, a.row_begin + yb, v0, m0, z0);
-    if (in1) resolve_pixel<CLIP>(a, x + 1, a.row_begin + yb, v1, m1, z1);
+    if (in0) resolve_pixel<CLIP, PEEL>(a, x, a.row_begin + yb, v0, m0, z0);
+    if (in1) resolve_pixel<CLIP, PEEL>(a, x + 1, a.row_begin + yb, v1, m1, z1);
     const int64_t oi = (int64_t)yb * a.stride + x;
+    [[maybe_unused]] uint32_t f0 = 0xFFFFFFFFu, f1 = 0xFFFFFFFFu;
+    if constexpr (PEEL) {
+        if (in0) peel_pixel(a, x, yb, oi, z0, f0);
+        if (in1) peel_pixel(a, x + 1, yb, oi + 1, z1, f1);
+    }
     if (VEC && in1) {
         const int64_t i = PBR_BOUNDS_PIXEL(oi, a.width, band_h, a.stride, 2, kBoundsOutput);
 #pragma unroll
         for (int k = 0; k < 14; ++k) *reinterpret_cast<float2*>(a.plane[k] + i) = make_float2(v0[k], v1[k]);
         *reinterpret_cast<uint32_t*>(a.material + i) = m0 | (m1 << 16);
         if (a.depth) *reinterpret_cast<float2*>(a.depth + i) = make_float2(z0, z1);
+        if constexpr (PEEL) *reinterpret_cast<uint2*>(a.prim_out + i) = make_uint2(f0, f1);
     } else {
         if (in0) {
             const int64_t i = PBR_BOUNDS_PIXEL(oi, a.width, band_h, a.stride, 1, kBoundsOutput);
@@ -866,6 +970,7 @@ __global__ __launch_bounds__(256) void raster_resolve_kernel(const RasterArgs a)
             for (int k = 0; k < 14; ++k) a.plane[k][i] = v0[k];
             a.material[i] = (uint16_t)m0;
             if (a.depth) a.depth[i] = z0;
+            if constexpr (PEEL) a.prim_out[i] = f0;
         }
         if (in1) {
             const int64_t i = PBR_BOUNDS_PIXEL(oi + 1, a.width, band_h, a.stride, 1, kBoundsOutput);
@@ -873,6 +978,7 @@ __global__ __launch_bounds__(256) void raster_resolve_kernel(const RasterArgs a)
             for (int k = 0; k < 14; ++k) a.plane[k][i] = v1[k];
             a.material[i] = (uint16_t)m1;
             if (a.depth) a.depth[i] = z1;
+            if constexpr (PEEL) a.prim_out[i] = f1;
         }
     }
 }
@@ -891,14 +997,18 @@ hipError_t launch_raster_setup(const RasterArgs& a, hipStream_t stream) {
     if (a.n_tris == 0u) return hipSuccess;
     const dim3 grid((uint32_t)(((uint64_t)a.n_tris + 255u) / 256u));
     if (a.clip_near) {
-        if (a.alpha_test)
-            hipLaunchKernelGGL((raster_setup_clip_kernel<true>), grid, dim3(256), 0, stream, a);
+        if (a.peel)
+            hipLaunchKernelGGL((raster_setup_clip_kernel<false, true>), grid, dim3(256), 0, stream, a);
+        else if (a.alpha_test)
+            hipLaunchKernelGGL((raster_setup_clip_kernel<true, false>), grid, dim3(256), 0, stream, a);
         else
-            hipLaunchKernelGGL((raster_setup_clip_kernel<false>), grid, dim3(256), 0, stream, a);
+            hipLaunchKernelGGL((raster_setup_clip_kernel<false, false>), grid, dim3(256), 0, stream, a);
+    } else if (a.peel) {
+        hipLaunchKernelGGL((raster_setup_kernel<false, true>), grid, dim3(256), 0, stream, a);
     } else if (a.alpha_test) {
-        hipLaunchKernelGGL((raster_setup_kernel<true>), grid, dim3(256), 0, stream, a);
+        hipLaunchKernelGGL((raster_setup_kernel<true, false>), grid, dim3(256), 0, stream, a);
     } else {
-        hipLaunchKernelGGL((raster_setup_kernel<false>), grid, dim3(256), 0, stream, a);
+        hipLaunchKernelGGL((raster_setup_kernel<false, false>), grid, dim3(256), 0, stream, a);
     }
     return hipGetLastError();
 }
@@ -908,14 +1018,18 @@ hipError_t launch_raster_large(const RasterArgs& a, hipStream_t stream) {
     const uint32_t gx = a.n_tris < (uint32_t)raster::kLargeGridX ? a.n_tris : (uint32_t)raster::kLargeGridX;
     const dim3 grid(gx, raster::kLargeSlabs);
     if (a.clip_near) {
-        if (a.alpha_test)
-            hipLaunchKernelGGL((raster_large_kernel<true, true>), grid, dim3(256), 0, stream, a);
+        if (a.peel)
+            hipLaunchKernelGGL((raster_large_kernel<true, false, true>), grid, dim3(256), 0, stream, a);
+        else if (a.alpha_test)
+            hipLaunchKernelGGL((raster_large_kernel<true, true, false>), grid, dim3(256), 0, stream, a);
         else
-            hipLaunchKernelGGL((raster_large_kernel<true, false>), grid, dim3(256), 0, stream, a);
+            hipLaunchKernelGGL((raster_large_kernel<true, false, false>), grid, dim3(256), 0, stream, a);
+    } else if (a.peel) {
+        hipLaunchKernelGGL((raster_large_kernel<false, false, true>), grid, dim3(256), 0, stream, a);
     } else if (a.alpha_test) {
-        hipLaunchKernelGGL((raster_large_kernel<false, true>), grid, dim3(256), 0, stream, a);
+        hipLaunchKernelGGL((raster_large_kernel<false, true, false>), grid, dim3(256), 0, stream, a);
     } else {
-        hipLaunchKernelGGL((raster_large_kernel<false, false>), grid, dim3(256), 0, stream, a);
+        hipLaunchKernelGGL((raster_large_kernel<false, false, false>), grid, dim3(256), 0, stream, a);
     }
     return hipGetLastError();
 }
@@ -924,15 +1038,26 @@ hipError_t launch_raster_resolve(const RasterArgs& a, hipStream_t stream) {
     const int band_h = a.row_end - a.row_begin;
     if (a.width <= 0 || band_h <= 0) return hipSuccess;
     const dim3 grid((a.width + 63) / 64, (band_h + 7) / 8);
-    if (a.clip_near) {
+    if (a.peel) {
+        if (a.clip_near) {
+            if (a.vec)
+                hipLaunchKernelGGL((raster_resolve_kernel<true, true, true>), grid, dim3(256), 0, stream, a);
+            else
+                hipLaunchKernelGGL((raster_resolve_kernel<false, true, true>), grid, dim3(256), 0, stream, a);
+        } else if (a.vec) {
+            hipLaunchKernelGGL((raster_resolve_kernel<true, false, true>), grid, dim3(256), 0, stream, a);
+        } else {
+            hipLaunchKernelGGL((raster_resolve_kernel<false, false, true>), grid, dim3(256), 0, stream, a);
+        }
+    } else if (a.clip_near) {
         if (a.vec)
-            hipLaunchKernelGGL((raster_resolve_kernel<true, true>), grid, dim3(256), 0, stream, a);
+            hipLaunchKernelGGL((raster_resolve_kernel<true, true, false>), grid, dim3(256), 0, stream, a);
         else
-            hipLaunchKernelGGL((raster_resolve_kernel<false, true>), grid, dim3(256), 0, stream, a);
+            hipLaunchKernelGGL((raster_resolve_kernel<false, true, false>), grid, dim3(256), 0, stream, a);
     } else if (a.vec) {
-        hipLaunchKernelGGL((raster_resolve_kernel<true, false>), grid, dim3(256), 0, stream, a);
+        hipLaunchKernelGGL((raster_resolve_kernel<true, false, false>), grid, dim3(256), 0, stream, a);
     } else {
-        hipLaunchKernelGGL((raster_resolve_kernel<false, false>), grid, dim3(256), 0, stream, a);
+        hipLaunchKernelGGL((raster_resolve_kernel<false, false, false>), grid, dim3(256), 0, stream, a);
     }
     return hipGetLastError();
 }

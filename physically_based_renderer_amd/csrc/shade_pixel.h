@@ -7,6 +7,7 @@
 
 #include <cstdint>
 
+#include "pbr_unorm.h"
 #include "shade_common.h"
 #include "shade_light_loops.h"
 
@@ -268,15 +269,7 @@ __device__ __forceinline__ float4 sky_pixel(f3 dir, const PassArgs& ps, const fl
     return sky_finish(sky_colour(dir, ps, sky), fast);
 }
 
-// D3D FLOAT -> UNORM8 (the R8G8B8A8_UNORM back buffer, d3dApp.h:124): NaN -> 0, clamp to [0, 1],
-// c * 255 + 0.5 in fp32 (no contraction), truncate.
-__device__ __forceinline__ uint32_t unorm8(float c) {
-    if (!(c == c)) return 0u;
-    c = c > 1.0f ? 1.0f : c;
-    c = c < 0.0f ? 0.0f : c;
-    return (uint32_t)(c * 255.0f + 0.5f);
-}
-
+// unorm8: the D3D FLOAT -> UNORM8 rule of the R8G8B8A8_UNORM back buffer (pbr_unorm.h).
 __device__ __forceinline__ void store_pixel(const FrameArgs& fr, int64_t off, float4 c) {
     off = PBR_BOUNDS_PIXEL(off, fr.width, fr.height, fr.out_stride, 1, kBoundsOutput);
     if (fr.format == kOutRgba8) {

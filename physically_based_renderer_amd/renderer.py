@@ -460,6 +460,10 @@ class ShadingContext:
     def rasterize_flags(self, draws: Sequence[Draw], view: View, flags, out=None, stream=None) -> Attributes:
         """:meth:`rasterize` through pbr_rasterize_flags with the given ``flags`` word (0: the same result as
         pbr_rasterize; an unknown bit raises ``PbrError(PBR_ERR_INVALID_ARGUMENT)``); ``flags`` None: pbr_rasterize."""
+        return self._rasterize(draws, view, flags, out, stream)
+
+    def _rasterize(self, draws, view, flags, out, stream, layer=None) -> Attributes:
+        """The three rasterising entry points behind one target set-up; ``layer``: a filled ``N.RasterLayer``."""
         v = view.to_c()
         rows = v.row_end - v.row_begin
         dev = torch.device("cuda", self.device)
@@ -485,7 +489,11 @@ class ShadingContext:
         t.row_stride = int(attrs.row_stride)
         meshes = getattr(self, "meshes", ())
         c_draws = (N.DrawDesc * max(len(draws), 1))(*[d.to_c(meshes) for d in draws])
-        if flags is None:
+        if layer is not None:
+            N.check(self.lib.pbr_rasterize_layer(self._h, c_draws, len(draws), ctypes.byref(v), ctypes.byref(t),
+                                                 int(flags), ctypes.byref(layer),
+                                                 ctypes.c_void_p(_stream_handle(stream))), "pbr_rasterize_layer", self._h)
+        elif flags is None:
             N.check(self.lib.pbr_rasterize(self._h, c_draws, len(draws), ctypes.byref(v), ctypes.byref(t),
                                            ctypes.c_void_p(_stream_handle(stream))), "pbr_rasterize", self._h)
         else:
@@ -518,6 +526,121 @@ class ShadingContext:
         N.check(self.lib.pbr_last_raster_alpha_stats(self._h, ctypes.byref(st), ctypes.c_void_p(_stream_handle(stream))),
                 "pbr_last_raster_alpha_stats", self._h)
         return {name: getattr(st, name) for name, _ in N.RasterAlphaStats._fields_}
+
+    def rasterize_layer(self, draws: Sequence[Draw], view: View, depth_in: torch.Tensor,
+                        prim_in: Optional[torch.Tensor] = None, flags: int = 0, out=None,
+                        prim_out: Optional[torch.Tensor] = None, stream=None):
+        """One layer of the transparent pass (pbr_rasterize_layer): per pixel the fragment of
+        ``draws`` with the smallest primitive ordinal among those at or past the floor ``prim_in`` ((H, row_stride)
+        int32 on the device; None: 0 everywhere, the first layer) and with z below ``depth_in`` ((H, row_stride)
+        float32). Returns ``(Attributes, prim_out)``: the attributes carry the new depth plane as ``.depth`` (the
+        winner's z; ``depth_in``'s value where the layer has no fragment, where the material is PBR_MATERIAL_NONE),
+        ``prim_out`` is the floor for the next layer. ``out``: an ``(Attributes, depth)`` pair; its depth plane may be
+        ``depth_in`` itself and ``prim_out`` may be ``prim_in``. Every layer of a sequence must pass the same ``draws``:
+        the ordinals are the call's own. ``flags``: 0 or PBR_RASTER_CLIP_NEAR."""
+        v = view.to_c()
+        rows = max(v.row_end - v.row_begin, 0)
+        dev = torch.device("cuda", self.device)
+        stride = depth_in.stride(0) if depth_in.dim() == 2 else view.width
+        if out is None:
+            out = (Attributes(torch.empty((N.NUM_ATTRIBUTE_PLANES, rows, stride), dtype=torch.float32, device=dev),
+                              torch.empty((rows, stride), dtype=torch.int16, device=dev), width=view.width),
+                   torch.empty((rows, stride), dtype=torch.float32, device=dev))
+        if isinstance(out, Attributes) or out[1] is None:
+            raise ValueError("a layer needs a depth plane: out must be an (Attributes, depth) pair")
+        if prim_out is None:
+            prim_out = torch.empty((rows, stride), dtype=torch.int32, device=dev)
+        self._check_device(depth_in, prim_in, prim_out)
+        for name, p, dtype in (("depth_in", depth_in, torch.float32), ("prim_in", prim_in, torch.int32),
+                               ("prim_out", prim_out, torch.int32)):
+            if p is not None and (p.dtype != dtype or p.dim() != 2 or p.stride(1) != 1 or p.shape[0] < rows or
+                                  p.shape[1] < view.width or p.stride(0) != out[0].row_stride):
+                raise ValueError(f"{name} must be an (H, W) {dtype} plane with the attribute planes' row stride")
+        layer = N.RasterLayer()
+        layer.depth_in = depth_in.data_ptr()
+        layer.prim_in = None if prim_in is None else prim_in.data_ptr()
+        layer.prim_out = prim_out.data_ptr()
+        return self._rasterize(draws, view, flags, out, stream, layer=layer), prim_out
+
+    def raster_layer_stats(self, stream=None) -> dict:
+        """pbr_last_raster_layer_stats of the last rasterisation on ``stream`` (synchronises it): layer_fragments, the
+        visibility updates a :meth:`rasterize_layer` issued (0: the layer is empty); zeros after any other call."""
+        st = N.RasterLayerStats()
+        N.check(self.lib.pbr_last_raster_layer_stats(self._h, ctypes.byref(st), ctypes.c_void_p(_stream_handle(stream))),
+                "pbr_last_raster_layer_stats", self._h)
+        return {name: getattr(st, name) for name, _ in N.RasterLayerStats._fields_}
+
+    def blend_layer(self, src: torch.Tensor, alpha: torch.Tensor, coverage: torch.Tensor, frame: torch.Tensor,
+                    width: Optional[int] = None, height: Optional[int] = None, stream=None) -> torch.Tensor:
+        """The transparent PSO's blend (pbr_blend_layer; PBRApp.cpp:831-842) of a shaded layer over ``frame``, in
+        place and asynchronously: where ``coverage`` ((H, >=W) uint8) is nonzero, colour = src * a + frame * (1 - a) and
+        alpha = a, with a from ``alpha`` ((H, >=W) float32: the resolved opacity plane). ``src``: (H, >=W, 4) float32;
+        ``frame``: (H, >=W, 4) float32 (RGBA32F) or uint8 (RGBA8_UNORM: inputs clamped to [0, 1], NaN -> 0). Pixels
+        with coverage 0 are neither read nor written in ``frame``."""
+        self._check_device(src, alpha, coverage, frame)
+        if frame.dtype == torch.uint8:
+            fmt = N.PBR_OUTPUT_RGBA8_UNORM
+        elif frame.dtype == torch.float32:
+            fmt = N.PBR_OUTPUT_RGBA32F
+        else:
+            raise ValueError("frame must be float32 (RGBA32F) or uint8 (RGBA8_UNORM)")
+        for name, t in (("src", src), ("frame", frame)):
+            if t.dim() != 3 or t.shape[2] != 4 or t.stride(2) != 1 or t.stride(1) != 4:
+                raise ValueError(f"{name} must be (H, W, 4) with contiguous pixels")
+        if src.dtype != torch.float32:
+            raise ValueError("src must be float32")
+        if alpha.dtype != torch.float32 or alpha.dim() != 2 or alpha.stride(1) != 1:
+            raise ValueError("alpha must be a (H, W) float32 plane with contiguous rows")
+        if coverage.dtype != torch.uint8 or coverage.dim() != 2 or coverage.stride(1) != 1:
+            raise ValueError("coverage must be a (H, W) uint8 tensor with contiguous rows")
+        h = min(src.shape[0], frame.shape[0]) if height is None else int(height)
+        w = min(src.shape[1], frame.shape[1]) if width is None else int(width)
+        for t in (src, alpha, coverage, frame):
+            if t.shape[0] < h or t.shape[1] < w:
+                raise ValueError("a plane is smaller than the blended rectangle")
+        b = N.BlendSource()
+        b.src, b.src_row_stride = src.data_ptr(), src.stride(0) // 4
+        b.alpha, b.alpha_row_stride = alpha.data_ptr(), alpha.stride(0)
+        b.coverage, b.coverage_row_stride = coverage.data_ptr(), coverage.stride(0)
+        f = N.FrameDesc()
+        f.out = frame.data_ptr()
+        f.out_row_stride = frame.stride(0) // 4
+        f.format = int(fmt)
+        N.check(self.lib.pbr_blend_layer(self._h, ctypes.byref(b), ctypes.byref(f), w, h,
+                                         ctypes.c_void_p(_stream_handle(stream))), "pbr_blend_layer", self._h)
+        return frame
+
+    def draw_transparent(self, draws: Sequence[Draw], view: View, depth: torch.Tensor, frame: torch.Tensor, *,
+                         flags: int = 0, filter: int = N.PBR_FILTER_POINT, max_layers: int = 8, stream=None):
+        """The reference's transparent pass (RenderLayer::Transparent, PBRApp.cpp:313-316) over a finished frame:
+        layer after layer, :meth:`rasterize_layer` -> :meth:`resolve` -> :meth:`shade` -> :meth:`blend_layer`, until a
+        layer is empty or ``max_layers`` layers were blended. ``depth``: the (H, row_stride) float32 depth plane of the
+        opaque and alpha-tested layers (1 where they drew nothing), updated in place to the depth after the pass;
+        ``frame``: the (H, W, 4) float32 or uint8 frame of the view's band, blended in place. The pass of
+        :meth:`set_pass` shades every layer (set ``PBR_FLAG_F0_PLANE``, as for any resolved G-buffer). Each layer
+        re-runs the vertex transform and the setup and shades the whole band. Returns ``(layers, stopped_on_empty)``:
+        how many layers were blended and whether the loop ended on an empty layer (False: ``max_layers`` was reached
+        and more may remain). Synchronises ``stream`` once per layer, to read the layer's counter."""
+        v = view.to_c()
+        rows = max(v.row_end - v.row_begin, 0)
+        dev = torch.device("cuda", self.device)
+        stride = depth.stride(0)
+        attrs = Attributes(torch.empty((N.NUM_ATTRIBUTE_PLANES, rows, stride), dtype=torch.float32, device=dev),
+                           torch.empty((rows, stride), dtype=torch.int16, device=dev), width=view.width)
+        prim = torch.empty((rows, stride), dtype=torch.int32, device=dev)
+        gb = GBuffer(torch.empty((N.NUM_PLANES, rows, view.width), dtype=torch.float32, device=dev),
+                     opacity=torch.empty((rows, view.width), dtype=torch.float32, device=dev))
+        coverage = torch.empty((rows, view.width), dtype=torch.uint8, device=dev)
+        shaded = torch.empty((rows, view.width, 4), dtype=torch.float32, device=dev)
+        for k in range(int(max_layers)):
+            self.rasterize_layer(draws, view, depth, prim if k else None, flags, out=(attrs, depth), prim_out=prim,
+                                 stream=stream)
+            if self.raster_layer_stats(stream)["layer_fragments"] == 0:
+                return k, True
+            self.resolve(attrs, filter, out=(gb, coverage), stream=stream)
+            self.shade(gb, shaded, stream=stream)
+            self.blend_layer(shaded, gb.opacity, coverage, frame, width=view.width, height=rows, stream=stream)
+        return int(max_layers), False
 
     def _check_device(self, *tensors) -> None:
         """Every tensor handed to the kernel must live on this context's device: a foreign pointer would be

@@ -7,7 +7,9 @@
                of the bottom row: spheres and floor cross the near plane. Only near-plane clipping
                (pbr_rasterize_flags with PBR_RASTER_CLIP_NEAR) draws those triangles;
   cutout       the reference scene with all 58 spheres under one alpha-tested material whose opacity map is a
-               256 x 256 checker with noise (libraries with PBR_RASTER_ALPHA_TEST only).
+               256 x 256 checker with noise (libraries with PBR_RASTER_ALPHA_TEST only);
+  glass        the reference scene plus four full-frame panes at decreasing depth in front of it, submitted far to
+               near: four layers of the transparent pass (libraries with pbr_rasterize_layer only; its legs are below).
 
 Four legs per scene:
   (a) the stages of one call, HIP events between them (pbr_debug_rasterize_timed): clears and table upload, the
@@ -22,6 +24,15 @@ Legs (a) and (b) are taken unflagged and then, when the library has pbr_rasteriz
 ("clip": true in the line), with the clip counters of the call; and, when it has PBR_RASTER_ALPHA_TEST, with that flag
 ("alpha": true) and the alpha counters: on the first three scenes under a table without a tested material (the cost
 of asking), on cutout against the same scene unflagged (the cost of the test).
+
+The glass scene's legs:
+  (e) the stages of one pbr_rasterize_layer call on the four panes (the first layer, over the opaque scene's depth)
+      beside the stages of the unflagged call on the same draws;
+  (f) pbr_blend_layer of a full frame (RGBA32F and RGBA8) beside a device-to-device copy that moves the same number
+      of bytes (the blend reads 37 and writes 16 bytes per RGBA32F pixel: a copy of 26.5 B per pixel);
+  (g) ShadingContext.draw_transparent whole -- four layers, each a rasterisation, a resolve, a shading pass over the
+      whole frame and a blend, plus the empty fifth rasterisation that ends the loop -- beside the opaque frame
+      (rasterize, resolve, shade_frame).
 
     python tools/raster_bench.py [--width 3840 --height 2160] [--steps 50] [--log profiles/r11/raster_bench.log]
 
@@ -112,6 +123,120 @@ def cutout_materials(n, seed=12):
     return [Material(flags=N.PBR_MAT_ALPHA_TEST, tex=(-1, -1, -1, -1, -1, 0)) for _ in range(n)], [tex]
 
 
+def glass_panes(n=4):
+    """n panes of 60 x 40 units around the overview camera's axis at z = -3, -5, ... (the camera is at z = -30, the
+    spheres around z = 0): each covers the whole frame; far to near in submission order."""
+    v = np.zeros((4, 14), np.float32)
+    v[:, 0], v[:, 1] = (-30.0, 30.0, 30.0, -30.0), (13.0, 13.0, -27.0, -27.0)
+    v[:, 5], v[:, 6], v[:, 10] = -1.0, 1.0, -1.0
+    v[:, 12], v[:, 13] = (0.0, 1.0, 1.0, 0.0), (0.0, 0.0, 1.0, 1.0)
+    mesh = Mesh(v, np.array([0, 1, 2, 0, 2, 3], np.uint32))
+    return mesh, [(-3.0 - 2.0 * k) for k in range(n)]
+
+
+def timed_layer_stages(ctx, draws, view, attrs, depth, depth_in, prim_out, steps):
+    """timed_stages for pbr_rasterize_layer (pbr_debug_rasterize_layer_timed): the first layer, prim_in NULL."""
+    timed = ctx.lib.pbr_debug_rasterize_layer_timed
+    timed.argtypes = [ctypes.c_void_p, ctypes.POINTER(N.DrawDesc), ctypes.c_int32, ctypes.POINTER(N.RasterView),
+                      ctypes.POINTER(N.RasterTargets), ctypes.c_uint32, ctypes.POINTER(N.RasterLayer), ctypes.c_void_p,
+                      ctypes.POINTER(ctypes.c_float)]
+    timed.restype = ctypes.c_int
+    v = view.to_c()
+    t = N.RasterTargets()
+    ps = attrs.planes.stride(0) * 4
+    t.planes[:] = [attrs.planes.data_ptr() + i * ps for i in range(14)]
+    t.material, t.depth, t.row_stride = attrs.material.data_ptr(), depth.data_ptr(), int(attrs.row_stride)
+    layer = N.RasterLayer()
+    layer.depth_in, layer.prim_in, layer.prim_out = depth_in.data_ptr(), None, prim_out.data_ptr()
+    c_draws = (N.DrawDesc * len(draws))(*[d.to_c(ctx.meshes) for d in draws])
+    stream = ctypes.c_void_p(int(torch.cuda.current_stream().cuda_stream))
+    ms = (ctypes.c_float * 5)()
+    rows = []
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < 0.2:  # clock ramp
+        ctx.rasterize_layer(draws, view, depth_in, None, out=(attrs, depth), prim_out=prim_out)
+    for _ in range(steps):
+        N.check(timed(ctx.handle, c_draws, len(draws), ctypes.byref(v), ctypes.byref(t), 0, ctypes.byref(layer), stream,
+                      ms), "pbr_debug_rasterize_layer_timed", ctx.handle)
+        rows.append(list(ms))
+    med = np.median(np.array(rows), axis=0)
+    return {k: float(x) for k, x in zip(STAGES, med)}
+
+
+def glass_legs(ctx, emit, cfg, ref_meshes, ref_draws, attrs, depth, steps):
+    """Legs (e), (f) and (g) of the glass scene."""
+    from physically_based_renderer_amd import envmap
+
+    W, H = cfg.width, cfg.height
+    dev = attrs.planes.device
+    view = S.reference_scene_view(cfg)
+    pane, zs = glass_panes()
+    n_opaque = len(ref_draws)
+    panes = [Draw(mesh=1, material=n_opaque + k, cull=1, world=S.translation(0.0, 0.0, z)) for k, z in enumerate(zs)]
+    ctx.set_meshes(ref_meshes + [pane])
+    ctx.set_materials([Material()] * n_opaque + [Material(diffuse_albedo=(0.3 + 0.2 * k, 0.6, 0.9 - 0.2 * k),
+                                                         roughness=0.4, opacity=0.2 + 0.1 * k) for k in range(len(zs))])
+    ctx.set_sky_map(envmap.procedural_sky_rgba16(128, 64))
+    pc = S.scene_pass(cfg)
+    pc.flags |= N.PBR_FLAG_F0_PLANE | N.PBR_FLAG_FAITHFUL
+    ctx.set_pass(pc)
+    ctx.rasterize(ref_draws, view, out=(attrs, depth))
+    depth0 = depth.clone()
+    prim = torch.empty((H, W), dtype=torch.int32, device=dev)
+    # (e) one layer call beside the unflagged call, both on the four panes
+    ctx.rasterize_layer(panes, view, depth0, None, out=(attrs, depth), prim_out=prim)
+    stats = ctx.raster_stats()
+    stats.update(ctx.raster_layer_stats())
+    emit({"scene": "glass", "leg": "e_layer_call", "stats": stats, "draws": len(panes),
+          "covered_pixels": int((attrs.material != -1).sum().item())})
+    for layer in (False, True):
+        st = (timed_layer_stages(ctx, panes, view, attrs, depth, depth0, prim, steps) if layer
+              else timed_stages(ctx, panes, view, attrs, depth, steps))
+        st.update(leg="e_stages_ms", scene="glass", layer=layer, coverage_ms=st["setup_small"] + st["large"])
+        emit(st)
+        fn = ((lambda: ctx.rasterize_layer(panes, view, depth0, None, out=(attrs, depth), prim_out=prim)) if layer
+              else (lambda: ctx.rasterize(panes, view, out=(attrs, depth))))
+        whole = event_ms(fn, steps)
+        whole.update(leg="e_whole_call", scene="glass", layer=layer)
+        emit(whole)
+    # (f) the blend beside a copy that moves as many bytes
+    ctx.rasterize_layer(panes, view, depth0, None, out=(attrs, depth), prim_out=prim)
+    gb, cov = ctx.resolve(attrs)
+    shaded = ctx.shade(gb)
+    for fmt, dtype, moved in (("rgba32f", torch.float32, 16 + 4 + 1 + 16 + 16), ("rgba8", torch.uint8, 16 + 4 + 1 + 4 + 4)):
+        frame = torch.zeros((H, W, 4), dtype=dtype, device=dev)
+        b = event_ms(lambda: ctx.blend_layer(shaded, gb.opacity, cov, frame), steps)
+        half = torch.empty(W * H * moved // 2, dtype=torch.uint8, device=dev)
+        other = torch.empty_like(half)
+        c = event_ms(lambda: other.copy_(half), steps)
+        b.update(leg="f_blend_layer", scene="glass", format=fmt, bytes_moved_per_pixel=moved,
+                 copy_same_bytes_median_ms=c["median_ms"], blend_over_copy=b["median_ms"] / c["median_ms"],
+                 covered_pixels=int((cov != 0).sum().item()))
+        emit(b)
+    # (g) the whole transparent pass beside the opaque frame
+    frame = torch.empty((H, W, 4), dtype=torch.float32, device=dev)
+
+    def opaque_frame():
+        at = ctx.rasterize(ref_draws, view, out=(attrs, depth))
+        ctx.resolve(at, out=(gb, cov))
+        ctx.shade_frame(gb, frame, coverage=cov)
+
+    done = []
+
+    def transparent():
+        depth.copy_(depth0)
+        done.append(ctx.draw_transparent(panes, view, depth, frame))
+
+    o = event_ms(opaque_frame, steps)
+    o.update(leg="g_opaque_frame", scene="glass")
+    emit(o)
+    opaque_frame()
+    t = event_ms(transparent, steps)
+    t.update(leg="g_draw_transparent", scene="glass", layers=done[-1][0], stopped_on_empty=done[-1][1],
+             per_layer_ms=t["median_ms"] / max(done[-1][0], 1), over_opaque_frame=t["median_ms"] / o["median_ms"])
+    emit(t)
+
+
 def timed_stages(ctx, draws, view, attrs, depth, steps, clip=False, alpha=False):
     """Per-stage medians of `steps` timed calls (each synchronises; the clock ramp is the untimed loop before)."""
     argtypes = [ctypes.c_void_p, ctypes.POINTER(N.DrawDesc), ctypes.c_int32, ctypes.POINTER(N.RasterView),
@@ -177,9 +302,10 @@ def main():
 
     can_clip = hasattr(N.lib(), "pbr_rasterize_flags")
     can_alpha = hasattr(N.lib(), "pbr_last_raster_alpha_stats")
+    can_layer = hasattr(N.lib(), "pbr_rasterize_layer")
     emit({"tool": "raster_bench", "width": W, "height": H, "sources_sha": info["sources_sha"],
           "checkout_sha": N.kernel_sources_sha(), "library": os.path.relpath(info["path"], ROOT),
-          "has_rasterize_flags": can_clip, "has_alpha_test": can_alpha,
+          "has_rasterize_flags": can_clip, "has_alpha_test": can_alpha, "has_rasterize_layer": can_layer,
           "device": torch.cuda.get_device_name(0), "steps": a.steps, "resolve_bytes_per_pixel": BYTES_WRITTEN})
     cfg = S.REFERENCE_SCENE.with_size(W, H).with_camera(*S.OVERVIEW_CAMERA)
     ref_meshes, ref_draws = S.reference_scene_draws(a.slices, a.stacks)
@@ -221,6 +347,8 @@ def main():
                 whole = event_ms(lambda: ctx.rasterize(draws, view, out=(attrs, depth), **kw), a.steps)
                 whole.update(leg="b_whole_call", scene=name, clip=clip, alpha=alpha)
                 emit(whole)
+        if can_layer:
+            glass_legs(ctx, emit, cfg, ref_meshes, ref_draws, attrs, depth, a.steps)
         host = []
         for _ in range(3):
             t0 = time.perf_counter()
