@@ -339,6 +339,39 @@ typedef struct pbr_gbuffer_targets {
 int pbr_resolve_materials(pbr_context* ctx, const pbr_attributes_soa* attrs, const pbr_gbuffer_targets* targets,
                           int32_t filter, void* stream);
 
+/* ---- Mip chains and the trilinear filter (additive: PBR_ABI_VERSION stays 9, detect by symbol) ----
+ * The reference samples every material map with g_SamAnisotropicWrap over texture->Resource->GetDesc().MipLevels
+ * levels (PBRApp.cpp:701, :1171-1178; Default.hlsl:80-105). Anisotropy stays parity-unpinned; the isotropic trilinear
+ * filter over chains this library builds itself is pinned bit for bit ("Mip chains and the trilinear
+ * filter", which fixes every operation).
+ *
+ * pbr_generate_mips builds the chains of every texture of the current material table on the device, the counterpart of
+ * the mips a DDS carries or a loader generates. Level 0 is the uploaded texture; level l >= 1 is
+ * max(1, W_(l-1) >> 1) x max(1, H_(l-1) >> 1), down to 1 x 1, each byte channel (alpha included) of a texel
+ * (a + b + c + d + 2) >> 2 of the texels of level l-1 at columns 2x, min(2x+1, W_(l-1)-1) and rows 2y,
+ * min(2y+1, H_(l-1)-1), from the stored bytes of that level. The chains belong to the table they were built from: a
+ * later pbr_set_materials invalidates them. Same rules as pbr_set_materials: the previous chains are released only
+ * after the queued resolves that read them (on any stream), `stream` is synchronised before the call returns, call it
+ * outside a graph capture. PBR_ERR_NOT_READY before pbr_set_materials. */
+int pbr_generate_mips(pbr_context* ctx, void* stream);
+
+/* pbr_resolve_materials with the trilinear filter on the five material maps (diffuse, specular, metallic, roughness,
+ * normal); the PBR_MAT_ALPHA_TEST opacity stays the level-0 point-wrap tap, everything else is pbr_resolve_materials's.
+ * For a geometry pixel (x, y) of the call with material m: the horizontal partner is (x^1, y), the vertical one
+ * (x, y^1); a partner is valid when it lies inside the call's width and height and its material id is m. dudx, dvdx =
+ * u, v at (x|1, y) minus at (x&~1, y), dudy, dvdy = at (x, y|1) minus at (x, y&~1); an invalid partner makes its pair
+ * +0 (no helper pixels across a silhouette or a material edge: level 0, the sharp choice). Per sampled texture of
+ * W x H texels and L levels: r2 = max((dudx W)^2 + (dvdx H)^2, (dudy W)^2 + (dvdy H)^2); lod = (r2 > 1 ? 0.5 *
+ * (exponent(r2) + mantissa(r2) * 2^-23) : 0) + lod_bias, clamped to [0, L-1]; the result is the lerp, by lod's
+ * fraction, of PBR_FILTER_LINEAR's bilinear at levels floor(lod) and min(floor(lod) + 1, L-1). With lod 0 it is
+ * PBR_FILTER_LINEAR's result bit for bit.
+ * Quads are aligned to the call's row 0 and column 0: a row band resolved through offset pointers equals the same
+ * rows of the full frame iff it starts on an even frame row and has an even height or ends with the frame.
+ * PBR_ERR_NOT_READY before pbr_generate_mips, and again after a pbr_set_materials until the chains are generated
+ * anew; PBR_ERR_INVALID_ARGUMENT also for a lod_bias that is NaN or infinite. */
+int pbr_resolve_materials_mip(pbr_context* ctx, const pbr_attributes_soa* attrs, const pbr_gbuffer_targets* targets,
+                              float lod_bias, void* stream);
+
 /* ---- Device rasteriser: indexed triangle meshes -> interpolated attributes ----------------------
  * VS (Default.hlsl:22-45) and the fixed-function rasteriser behind DrawIndexedInstanced (PBRApp.cpp:1133) under the
  * reference's PSO state (CD3DX12_RASTERIZER_DESC(D3D12_DEFAULT), CD3DX12_DEPTH_STENCIL_DESC(D3D12_DEFAULT),

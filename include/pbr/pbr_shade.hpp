@@ -374,6 +374,24 @@ class ShadingContext {
         t.coverage_row_stride = coverage_row_stride;
         Check(pbr_resolve_materials(ctx_, &attrs, &t, filter, stream), "pbr_resolve_materials");
     }
+    // The mip chains of the current material table's textures (pbr_generate_mips; the MipLevels of the reference's
+    // textures, PBRApp.cpp:701, :1171-1178); again after every SetMaterials.
+    void GenerateMips(hipStream_t stream = nullptr) { Check(pbr_generate_mips(ctx_, stream), "pbr_generate_mips"); }
+    // ResolveMaterials with the trilinear filter over those chains (pbr_resolve_materials_mip; Default.hlsl:80-105).
+    // A band must start on an even row of the frame and have an even height or end with the frame.
+    void ResolveMaterialsMip(const pbr_attributes_soa& attrs, DeviceGBuffer& gb, int32_t row_begin, float lod_bias = 0.0f,
+                             float* opacity = nullptr, uint8_t* coverage = nullptr, int64_t coverage_row_stride = 0,
+                             hipStream_t stream = nullptr) {
+        pbr_gbuffer_targets t;
+        std::memset(&t, 0, sizeof t);
+        const size_t off = static_cast<size_t>(row_begin) * gb.row_stride();
+        for (int i = 0; i < DeviceGBuffer::kPlanes; ++i) t.planes[i] = gb.plane(i) + off;
+        t.opacity = opacity;
+        t.coverage = coverage;
+        t.row_stride = gb.row_stride();
+        t.coverage_row_stride = coverage_row_stride;
+        Check(pbr_resolve_materials_mip(ctx_, &attrs, &t, lod_bias, stream), "pbr_resolve_materials_mip");
+    }
 
     // The meshes Rasterize draws from (BuildShapeGeometry's vertex / index buffer uploads): host data, reusable on
     // return.

@@ -47,6 +47,46 @@ struct ResolveArgs {
 };
 hipError_t launch_resolve_materials(const ResolveArgs& a, hipStream_t stream);
 
+// ---- Mip chains and the trilinear resolve (material_resolve.h; pbr_generate_mips, pbr_resolve_materials_mip) ------
+// The chains of a material table live beside it, in a resource of their own: level 0 of a texture stays where the
+// upload put it (MaterialRec::tex), its levels 1 .. L-1 are consecutive MaterialTex entries of a level table whose
+// offsets count dwords of the chains' own texel buffer. A material finds its chains through a table parallel to the
+// material table: five MipSlot per material, in MaterialRec::tex order (the opacity map is only ever tapped at
+// level 0); an unused slot is {0, 1}.
+struct MipSlot {
+    uint32_t first;  // the level table entry of level 1
+    int32_t levels;  // L = floor(log2(max(W0, H0))) + 1
+};
+// One texture in one launch of the generation: where the level before it and the new level are, and how many texels
+// of the launch come before this texture's.
+struct MipGen {
+    uint32_t src, dst;  // first texel of either level in its buffer
+    int32_t sw, sh, dw, dh;
+    uint32_t first;
+    uint32_t pad;
+};
+struct MipGenArgs {
+    const MipGen* gen;  // the textures that have this level, `first` ascending
+    int n;
+    uint32_t n_out;       // texels of the launch
+    const uint32_t* src;  // level 1: the upload's texel buffer; later levels: the chains'
+    int64_t n_src;
+    uint32_t* dst;
+    int64_t n_dst;
+};
+hipError_t launch_generate_mip_level(const MipGenArgs& a, hipStream_t stream);
+
+struct ResolveMipArgs {
+    ResolveArgs r;  // r.linear is not read
+    const MipSlot* slots;  // 5 * r.n_materials
+    const MaterialTex* levels;
+    int64_t n_levels;
+    const uint32_t* mip_texels;
+    int64_t n_mip_texels;
+    float lod_bias;
+};
+hipError_t launch_resolve_materials_mip(const ResolveMipArgs& a, hipStream_t stream);
+
 // ---- Rasteriser (raster.h; pbr_rasterize) ---------------------------------------------------------
 // One draw on the device: its constants and where its data is.
 struct RasterDraw {

@@ -17,6 +17,13 @@
 // Textures: every texture is repacked to RGBA8 at upload (pbr_set_materials: a 1-channel texture replicates .r
 // into .rgb, a 3-channel one gets alpha 255), all of them in one dword buffer, so a tap is one aligned dword load
 // whatever the channel count. A channel decodes as (float)u8 / 255.0f, correctly rounded.
+//
+// Mip chains and the trilinear filter (pbr_generate_mips, pbr_resolve_materials_mip; the reference samples its maps over
+// texture->Resource->GetDesc().MipLevels levels, PBRApp.cpp:701, :1171-1178, Default.hlsl:80-105): the chains are built
+// by generate_mip_level_kernel, one launch per level; resolve_materials_mip_kernel is the same tile, pixel pair per
+// lane and record paths as resolve_materials_kernel, with the level of detail of each sampled texture taken from the
+// differences of u and v inside the 2 x 2 pixel quad a wave holds: across the lane's own pair, and across lanes L and
+// L ^ 32 (the rows y and y ^ 1) through one half-wave swap per value.
 #pragma once
 
 #include "pbr_device_math.h"
@@ -72,39 +79,105 @@ __device__ __forceinline__ void sample(const uint32_t* texels, int64_t n_texels,
     }
 }
 
-// Default.hlsl:50-116 for one geometry pixel with material record `m` (a wave-uniform or a per-lane reference).
+// The point or the linear filter on level 0: the sampler of resolve_materials_kernel.
 template <bool LINEAR>
+struct LevelZero {
+    // NCH channels of the material's map `slot` (its tex[] index), whose level 0 is `t` in `texels`.
+    template <int NCH>
+    __device__ __forceinline__ void fetch(const uint32_t* texels, int64_t n_texels, const MaterialTex& t, int slot,
+                                          float u, float v, float* out) const {
+        sample<NCH, LINEAR>(texels, n_texels, t, u, v, out);
+    }
+};
+
+// The screen-space differences of (u, v) at a pixel: right minus left and bottom minus top inside its
+// 2 x 2 quad, +0 where the partner is outside the frame or has another material.
+struct Footprint {
+    float dudx, dvdx, dudy, dvdy;
+};
+
+// The trilinear filter over a material's mip chains: the sampler of resolve_materials_mip_kernel. `slots`: the five
+// MipSlot of the pixel's material.
+struct Trilinear {
+    const ResolveMipArgs& a;
+    const MipSlot* slots;
+    Footprint d;
+    template <int NCH>
+    __device__ __forceinline__ void fetch(const uint32_t*, int64_t, const MaterialTex& t, int slot, float u, float v,
+                                          float* out) const {
+        const MipSlot chain = slots[slot];
+        const int last = chain.levels - 1;
+        const float ax = d.dudx * (float)t.w, ay = d.dvdx * (float)t.h;
+        const float bx = d.dudy * (float)t.w, by = d.dvdy * (float)t.h;
+        const float rx = ax * ax + ay * ay, ry = bx * bx + by * by;
+        const float r2 = ry > rx ? ry : rx;
+        float base = 0.0f;
+        if (r2 > 1.0f) {  // false for NaN; the piecewise-linear log2: exponent plus mantissa fraction
+            const uint32_t b = __float_as_uint(r2);
+            const float l2 = (float)((int)(b >> 23) - 127) + (float)(b & 0x7FFFFFu) * 0x1p-23f;
+            base = 0.5f * l2;
+        }
+        float lod = base + a.lod_bias;
+        if (lod < 0.0f) lod = 0.0f;
+        if (lod > (float)last) lod = (float)last;
+        const int l0 = (int)floorf(lod);
+        const float f = lod - (float)l0;
+        level<NCH>(t, chain, l0, u, v, out);
+        if (f != 0.0f) {  // f == 0: c0 + 0 * (c1 - c0) has c0's bits
+            const int l1 = l0 + 1 < last ? l0 + 1 : last;
+            float c1[NCH];
+            level<NCH>(t, chain, l1, u, v, c1);
+#pragma unroll
+            for (int c = 0; c < NCH; ++c) out[c] = hlerp(out[c], c1[c], f);
+        }
+    }
+    // The linear-wrap bilinear of level l: level 0 in the upload's buffer, the others in the chains'.
+    template <int NCH>
+    __device__ __forceinline__ void level(const MaterialTex& t, const MipSlot& chain, int l, float u, float v,
+                                          float* out) const {
+        if (l == 0) {
+            sample<NCH, true>(a.r.texels, a.r.n_texels, t, u, v, out);
+        } else {
+            const MaterialTex tl = a.levels[PBR_BOUNDS((int64_t)chain.first + (l - 1), a.n_levels, kBoundsTexel)];
+            sample<NCH, true>(a.mip_texels, a.n_mip_texels, tl, u, v, out);
+        }
+    }
+};
+
+// Default.hlsl:50-116 for one geometry pixel with material record `m` (a wave-uniform or a per-lane reference); `s`
+// samples its five maps.
+template <class Sampler>
 __device__ __forceinline__ void resolve_pixel(const MaterialRec& m, const uint32_t* texels, int64_t n_texels,
-                                              const PixelIn& in, PixelOut& o) {
+                                              const PixelIn& in, PixelOut& o, const Sampler& s) {
     const uint32_t flags = m.flags;
     // pin.NormalW = normalize(pin.NormalW) (Default.hlsl:50): a zero vector gives NaN, as there
     const float nx = in.a[kInN], ny = in.a[kInN + 1], nz = in.a[kInN + 2];
     const float len = sqrtf((nx * nx + ny * ny) + nz * nz);
     const float nw[3] = {nx / len, ny / len, nz / len};
     if (flags & kMatDiffuseTexture) {
-        sample<3, LINEAR>(texels, n_texels, m.tex[0], in.a[kInU], in.a[kInV], o.alb);
+        s.template fetch<3>(texels, n_texels, m.tex[0], 0, in.a[kInU], in.a[kInV], o.alb);
     } else {
 #pragma unroll
         for (int c = 0; c < 3; ++c) o.alb[c] = m.diffuse[c];
     }
     if (flags & kMatMetallicTexture)
-        sample<1, LINEAR>(texels, n_texels, m.tex[2], in.a[kInU], in.a[kInV], &o.metal);
+        s.template fetch<1>(texels, n_texels, m.tex[2], 2, in.a[kInU], in.a[kInV], &o.metal);
     else
         o.metal = m.metallic;
     if (flags & kMatSpecularTexture) {
-        sample<3, LINEAR>(texels, n_texels, m.tex[1], in.a[kInU], in.a[kInV], o.f0);
+        s.template fetch<3>(texels, n_texels, m.tex[1], 1, in.a[kInU], in.a[kInV], o.f0);
     } else {
 #pragma unroll
         for (int c = 0; c < 3; ++c) o.f0[c] = hlerp(m.fresnel[c], o.alb[c], o.metal);  // Default.hlsl:94-95
     }
     if (flags & kMatRoughnessTexture)
-        sample<1, LINEAR>(texels, n_texels, m.tex[3], in.a[kInU], in.a[kInV], &o.rough);
+        s.template fetch<1>(texels, n_texels, m.tex[3], 3, in.a[kInU], in.a[kInV], &o.rough);
     else
         o.rough = m.roughness;
     if (flags & kMatNormalTexture) {  // NormalSampleToWorldSpace (LightingUtil.hlsl:203-214), not renormalised
-        float s[3];
-        sample<3, LINEAR>(texels, n_texels, m.tex[4], in.a[kInU], in.a[kInV], s);
-        const float ntx = 2.0f * s[0] - 1.0f, nty = 2.0f * s[1] - 1.0f, ntz = 2.0f * s[2] - 1.0f;
+        float smp[3];
+        s.template fetch<3>(texels, n_texels, m.tex[4], 4, in.a[kInU], in.a[kInV], smp);
+        const float ntx = 2.0f * smp[0] - 1.0f, nty = 2.0f * smp[1] - 1.0f, ntz = 2.0f * smp[2] - 1.0f;
 #pragma unroll
         for (int c = 0; c < 3; ++c)  // mul(normalT, TBN)
             o.n[c] = (ntx * in.a[kInT + c] + nty * in.a[kInB + c]) + ntz * nw[c];
@@ -128,6 +201,36 @@ __device__ __forceinline__ void background_pixel(const PixelIn& in, PixelOut& o)
     o.rough = 1.0f;
     o.opacity = 1.0f;
     o.cov = 0u;
+}
+
+// A value of the wave's two rows: .x from the even row (lanes 0-31), .y from the odd one (lanes 32-63), in every lane
+// of both. One v_permlane32_swap; every lane of the wave must call it.
+__device__ __forceinline__ uint2 quad_rows(uint32_t v) {
+    const auto r = __builtin_amdgcn_permlane32_swap(v, v, false, false);
+    return make_uint2(r[0], r[1]);
+}
+__device__ __forceinline__ float rows_difference(float v) {  // bottom minus top
+    const uint2 r = quad_rows(__float_as_uint(v));
+    return __uint_as_float(r.y) - __uint_as_float(r.x);
+}
+
+// The footprints of both pixels of a lane. Every lane of the wave must call it. A partner outside the frame carries id
+// 0xFFFF, which no geometry pixel has: comparing ids is the whole validity test of a geometry pixel's partner (a
+// background pixel's footprint is never read).
+__device__ __forceinline__ void quad_footprints(const PixelIn& p0, const PixelIn& p1, uint32_t id0, uint32_t id1,
+                                                Footprint d[2]) {
+    const float dudy0 = rows_difference(p0.a[kInU]), dvdy0 = rows_difference(p0.a[kInV]);
+    const float dudy1 = rows_difference(p1.a[kInU]), dvdy1 = rows_difference(p1.a[kInV]);
+    const uint2 ids = quad_rows(id0 | (id1 << 16));
+    const bool h = id0 == id1, v0 = (ids.x & 0xFFFFu) == (ids.y & 0xFFFFu), v1 = (ids.x >> 16) == (ids.y >> 16);
+    const float dudx = h ? p1.a[kInU] - p0.a[kInU] : 0.0f, dvdx = h ? p1.a[kInV] - p0.a[kInV] : 0.0f;
+    d[0] = Footprint{dudx, dvdx, v0 ? dudy0 : 0.0f, v0 ? dvdy0 : 0.0f};
+    d[1] = Footprint{dudx, dvdx, v1 ? dudy1 : 0.0f, v1 ? dvdy1 : 0.0f};
+}
+
+// The sampler of a pixel with material `id` (wave-uniform or per lane) and footprint `d`.
+__device__ __forceinline__ Trilinear trilinear(const ResolveMipArgs& a, uint32_t id, const Footprint& d) {
+    return {a, a.slots + PBR_BOUNDS((int64_t)id * 5, (int64_t)a.r.n_materials * 5, kBoundsTexel), d};
 }
 
 }  // namespace resolve
@@ -177,6 +280,7 @@ __global__ __launch_bounds__(256) void resolve_materials_kernel(const ResolveArg
     }
     const bool g0 = in0 && id0 < n_mat, g1 = in1 && id1 < n_mat;
 
+    const LevelZero<LINEAR> level0;
     PixelOut o0, o1;
     background_pixel(p0, o0);
     background_pixel(p1, o1);
@@ -189,15 +293,15 @@ __global__ __launch_bounds__(256) void resolve_materials_kernel(const ResolveArg
         const bool differs = (g0 && id0 != first) || (g1 && id1 != first);
         if (__ballot(differs) == 0) {
             const MaterialRec& m = a.table[PBR_BOUNDS((int64_t)first, (int64_t)n_mat, kBoundsTexel)];
-            if (g0) resolve_pixel<LINEAR>(m, a.texels, a.n_texels, p0, o0);
-            if (g1) resolve_pixel<LINEAR>(m, a.texels, a.n_texels, p1, o1);
+            if (g0) resolve_pixel(m, a.texels, a.n_texels, p0, o0, level0);
+            if (g1) resolve_pixel(m, a.texels, a.n_texels, p1, o1, level0);
         } else {
             if (g0)
-                resolve_pixel<LINEAR>(a.table[PBR_BOUNDS((int64_t)id0, (int64_t)n_mat, kBoundsTexel)], a.texels,
-                                      a.n_texels, p0, o0);
+                resolve_pixel(a.table[PBR_BOUNDS((int64_t)id0, (int64_t)n_mat, kBoundsTexel)], a.texels, a.n_texels,
+                              p0, o0, level0);
             if (g1)
-                resolve_pixel<LINEAR>(a.table[PBR_BOUNDS((int64_t)id1, (int64_t)n_mat, kBoundsTexel)], a.texels,
-                                      a.n_texels, p1, o1);
+                resolve_pixel(a.table[PBR_BOUNDS((int64_t)id1, (int64_t)n_mat, kBoundsTexel)], a.texels, a.n_texels,
+                              p1, o1, level0);
         }
     }
 
@@ -235,6 +339,161 @@ __global__ __launch_bounds__(256) void resolve_materials_kernel(const ResolveArg
                     (uint8_t)o1.cov;
         }
     }
+}
+
+// pbr_resolve_materials_mip: resolve_materials_kernel's tile, accesses and record paths around the trilinear sampler;
+// what is added is the footprint exchange between the loads and the resolve.
+template <bool VEC>
+__global__ __launch_bounds__(256) void resolve_materials_mip_kernel(const ResolveMipArgs ma) {
+    using namespace resolve;
+    const ResolveArgs& a = ma.r;
+    const int x = (int)blockIdx.x * kResolveTileW + (int)(threadIdx.x & 31u) * 2;
+    const int y = (int)blockIdx.y * kResolveTileH + (int)(threadIdx.x >> 5);
+    const bool in0 = y < a.height && x < a.width, in1 = y < a.height && x + 1 < a.width;
+    const bool pair = VEC && in1;  // both pixels through one 8-byte access per plane
+    const int64_t ii = (int64_t)y * a.in_stride + x;
+    const uint32_t n_mat = (uint32_t)a.n_materials;
+
+    uint32_t id0 = 0xFFFFu, id1 = 0xFFFFu;
+    PixelIn p0{}, p1{};
+    if (pair) {
+        const int64_t i = PBR_BOUNDS_PIXEL(ii, a.width, a.height, a.in_stride, 2, kBoundsGBuffer);
+        const uint32_t two = *reinterpret_cast<const uint32_t*>(a.material + i);
+        id0 = two & 0xFFFFu;
+        id1 = two >> 16;
+        float* q0 = p0.a;
+        float* q1 = p1.a;
+#pragma unroll
+        for (int k = 0; k < 14; ++k) {
+            const float2 v = *reinterpret_cast<const float2*>(a.attr[k] + i);
+            q0[k] = v.x;
+            q1[k] = v.y;
+        }
+    } else {
+        if (in0) {
+            const int64_t i = PBR_BOUNDS_PIXEL(ii, a.width, a.height, a.in_stride, 1, kBoundsGBuffer);
+            id0 = a.material[i];
+            float* q0 = p0.a;
+#pragma unroll
+            for (int k = 0; k < 14; ++k) q0[k] = a.attr[k][i];
+        }
+        if (in1) {
+            const int64_t i = PBR_BOUNDS_PIXEL(ii + 1, a.width, a.height, a.in_stride, 1, kBoundsGBuffer);
+            id1 = a.material[i];
+            float* q1 = p1.a;
+#pragma unroll
+            for (int k = 0; k < 14; ++k) q1[k] = a.attr[k][i];
+        }
+    }
+    const bool g0 = in0 && id0 < n_mat, g1 = in1 && id1 < n_mat;
+    // Every lane of the wave gets here together (pixels outside the frame and background pixels included), ahead of
+    // the divergent branches below: the wave's two rows exchange u, v and the ids.
+    Footprint d[2];
+    quad_footprints(p0, p1, id0, id1, d);
+
+    PixelOut o0, o1;
+    background_pixel(p0, o0);
+    background_pixel(p1, o1);
+    // One material for the whole wave? Every geometry pixel's id against the first geometry lane's.
+    const uint32_t key = g0 ? id0 : g1 ? id1 : 0xFFFFFFFFu;
+    const uint64_t any = __ballot(key != 0xFFFFFFFFu);
+    if (any != 0) {
+        const int lead = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(any));
+        const uint32_t first = (uint32_t)__builtin_amdgcn_readlane((int)key, lead);
+        const bool differs = (g0 && id0 != first) || (g1 && id1 != first);
+        if (__ballot(differs) == 0) {
+            const MaterialRec& m = a.table[PBR_BOUNDS((int64_t)first, (int64_t)n_mat, kBoundsTexel)];
+            if (g0) resolve_pixel(m, a.texels, a.n_texels, p0, o0, trilinear(ma, first, d[0]));
+            if (g1) resolve_pixel(m, a.texels, a.n_texels, p1, o1, trilinear(ma, first, d[1]));
+        } else {
+            if (g0)
+                resolve_pixel(a.table[PBR_BOUNDS((int64_t)id0, (int64_t)n_mat, kBoundsTexel)], a.texels, a.n_texels,
+                              p0, o0, trilinear(ma, id0, d[0]));
+            if (g1)
+                resolve_pixel(a.table[PBR_BOUNDS((int64_t)id1, (int64_t)n_mat, kBoundsTexel)], a.texels, a.n_texels,
+                              p1, o1, trilinear(ma, id1, d[1]));
+        }
+    }
+
+    // pbr_gbuffer_soa order: pos xyz, normal xyz, albedo rgb, metallic, roughness, ao, f0 rgb
+    const float v0[15] = {p0.a[0], p0.a[1], p0.a[2], o0.n[0], o0.n[1], o0.n[2], o0.alb[0], o0.alb[1],
+                          o0.alb[2], o0.metal, o0.rough, 1.0f, o0.f0[0], o0.f0[1], o0.f0[2]};
+    const float v1[15] = {p1.a[0], p1.a[1], p1.a[2], o1.n[0], o1.n[1], o1.n[2], o1.alb[0], o1.alb[1],
+                          o1.alb[2], o1.metal, o1.rough, 1.0f, o1.f0[0], o1.f0[1], o1.f0[2]};
+    const int64_t oi = (int64_t)y * a.out_stride + x, ci = (int64_t)y * a.cov_stride + x;
+    if (pair) {
+        const int64_t i = PBR_BOUNDS_PIXEL(oi, a.width, a.height, a.out_stride, 2, kBoundsOutput);
+#pragma unroll
+        for (int k = 0; k < 15; ++k) *reinterpret_cast<float2*>(a.plane[k] + i) = make_float2(v0[k], v1[k]);
+        if (a.opacity) *reinterpret_cast<float2*>(a.opacity + i) = make_float2(o0.opacity, o1.opacity);
+        if (a.coverage)
+            *reinterpret_cast<uint16_t*>(a.coverage +
+                                         PBR_BOUNDS_PIXEL(ci, a.width, a.height, a.cov_stride, 2, kBoundsCoverage)) =
+                (uint16_t)(o0.cov | (o1.cov << 8));
+    } else {
+        if (in0) {
+            const int64_t i = PBR_BOUNDS_PIXEL(oi, a.width, a.height, a.out_stride, 1, kBoundsOutput);
+#pragma unroll
+            for (int k = 0; k < 15; ++k) a.plane[k][i] = v0[k];
+            if (a.opacity) a.opacity[i] = o0.opacity;
+            if (a.coverage)
+                a.coverage[PBR_BOUNDS_PIXEL(ci, a.width, a.height, a.cov_stride, 1, kBoundsCoverage)] = (uint8_t)o0.cov;
+        }
+        if (in1) {
+            const int64_t i = PBR_BOUNDS_PIXEL(oi + 1, a.width, a.height, a.out_stride, 1, kBoundsOutput);
+#pragma unroll
+            for (int k = 0; k < 15; ++k) a.plane[k][i] = v1[k];
+            if (a.opacity) a.opacity[i] = o1.opacity;
+            if (a.coverage)
+                a.coverage[PBR_BOUNDS_PIXEL(ci + 1, a.width, a.height, a.cov_stride, 1, kBoundsCoverage)] =
+                    (uint8_t)o1.cov;
+        }
+    }
+}
+
+// One level of every chain that has it (pbr_generate_mips): a lane per texel of the level, its texture
+// found from the prefix of texel counts; each byte channel is (a + b + c + d + 2) >> 2 of the 2 x 2 texels of the
+// level before, columns and rows clamped to its last. Even and odd bytes are summed in 16-bit fields of two dwords
+// (a sum is at most 1022).
+__global__ __launch_bounds__(256) void generate_mip_level_kernel(const MipGenArgs a) {
+    const uint32_t g = blockIdx.x * 256u + threadIdx.x;
+    if (g >= a.n_out) return;
+    int lo = 0, hi = a.n;  // the largest i with gen[i].first <= g
+    for (int it = 0; it < 32 && hi - lo > 1; ++it) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (a.gen[PBR_BOUNDS((int64_t)mid, (int64_t)a.n, kBoundsTexel)].first <= g)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    const MipGen t = a.gen[PBR_BOUNDS((int64_t)lo, (int64_t)a.n, kBoundsTexel)];
+    const uint32_t k = g - t.first;
+    const int x = (int)(k % (uint32_t)t.dw), y = (int)(k / (uint32_t)t.dw);
+    const int x0 = 2 * x, x1 = x0 + 1 < t.sw ? x0 + 1 : t.sw - 1, y0 = 2 * y, y1 = y0 + 1 < t.sh ? y0 + 1 : t.sh - 1;
+    auto src = [&](int ty, int tx) {
+        return a.src[PBR_BOUNDS((int64_t)t.src + (int64_t)(ty * t.sw + tx), a.n_src, kBoundsTexel)];
+    };
+    const uint32_t t00 = src(y0, x0), t10 = src(y0, x1), t01 = src(y1, x0), t11 = src(y1, x1);
+    constexpr uint32_t kEven = 0x00FF00FFu, kHalf = 0x00020002u;
+    const uint32_t even = (t00 & kEven) + (t10 & kEven) + (t01 & kEven) + (t11 & kEven) + kHalf;
+    const uint32_t odd = ((t00 >> 8) & kEven) + ((t10 >> 8) & kEven) + ((t01 >> 8) & kEven) + ((t11 >> 8) & kEven) + kHalf;
+    a.dst[PBR_BOUNDS((int64_t)t.dst + (int64_t)k, a.n_dst, kBoundsTexel)] = ((even >> 2) & kEven) | (((odd >> 2) & kEven) << 8);
+}
+
+hipError_t launch_generate_mip_level(const MipGenArgs& a, hipStream_t stream) {
+    if (a.n <= 0 || a.n_out == 0) return hipSuccess;
+    hipLaunchKernelGGL(generate_mip_level_kernel, dim3((a.n_out + 255u) / 256u), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_resolve_materials_mip(const ResolveMipArgs& a, hipStream_t stream) {
+    if (a.r.width <= 0 || a.r.height <= 0) return hipSuccess;
+    const dim3 grid((a.r.width + kResolveTileW - 1) / kResolveTileW, (a.r.height + kResolveTileH - 1) / kResolveTileH);
+    if (a.r.vec)
+        hipLaunchKernelGGL((resolve_materials_mip_kernel<true>), grid, dim3(256), 0, stream, a);
+    else
+        hipLaunchKernelGGL((resolve_materials_mip_kernel<false>), grid, dim3(256), 0, stream, a);
+    return hipGetLastError();
 }
 
 hipError_t launch_resolve_materials(const ResolveArgs& a, hipStream_t stream) {

@@ -104,11 +104,30 @@ struct pbr_context {
         int n = 0;
         int64_t n_texels = 0;
         std::vector<uint32_t> flags;  // n
+        // What pbr_generate_mips builds the chains from: where each texture of the upload is, and the texture of each
+        // material's six slots (6 n; -1: unused).
+        std::vector<pbr::MaterialTex> place;
+        std::vector<int32_t> slot_tex;
         bool set = false;
         Resource use;
         explicit Materials(std::vector<Resource*>& l) : use(l, &d_table, &d_texels) {}
     };
     Materials mats{resources};
+    // The mip chains of the material table's textures (pbr_generate_mips; read by pbr_resolve_materials_mip), a resource
+    // of their own: one block holding the materials' MipSlot table and, behind it, the level table (then the launch
+    // tables of the generation), and the texel buffer of the levels >= 1. They belong to the table they were built
+    // from: pbr_set_materials clears `set`.
+    struct Mips {
+        char* d_tables = nullptr;
+        uint32_t* d_texels = nullptr;
+        const pbr::MipSlot* d_slots = nullptr;      // inside d_tables
+        const pbr::MaterialTex* d_levels = nullptr;  // inside d_tables
+        int64_t n_levels = 0, n_texels = 0;
+        bool set = false;
+        Resource use;
+        explicit Mips(std::vector<Resource*>& l) : use(l, &d_tables, &d_texels) {}
+    };
+    Mips mips{resources};
     // The meshes pbr_rasterize draws from (pbr_set_meshes): every mesh's vertices in one buffer, every index in
     // another, replaced as a whole; the placement of each mesh stays on the host.
     struct MeshPlace {

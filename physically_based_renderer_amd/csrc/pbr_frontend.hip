@@ -2,6 +2,7 @@
 // material resolve and the rasteriser. Host code only; the kernels live in frontend_kernels.hip, the context and the
 // ordering protocol in pbr_context.hip (pbr_context_impl.h).
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <utility>
 
@@ -11,6 +12,8 @@
 
 extern "C" __attribute__((used, visibility("default"))) const char pbr_unit_info_pbr_frontend[] =
     PBR_UNIT_INFO("pbr_frontend", PBR_BI_SWITCH(PBR_DEBUG_BOUNDS));
+
+static size_t align_up(size_t n, size_t a) { return (n + a - 1) / a * a; }
 
 // Replace both buffers of `r` (a set that is uploaded as a whole) by copies of the host arrays src0 and src1.
 static int replace_pair(Entry& en, Resource& r, const void* src0, size_t bytes0, const void* src1, size_t bytes1,
@@ -49,6 +52,7 @@ int pbr_set_materials(pbr_context* ctx, const pbr_material* materials, int32_t n
     static const int slot_of_bit[6] = {0, 1, 2, 3, 4, 5};
     std::vector<pbr::MaterialRec> recs((size_t)(n_materials > 0 ? n_materials : 1));
     std::memset(recs.data(), 0, sizeof(pbr::MaterialRec) * recs.size());
+    std::vector<int32_t> slot_tex((size_t)n_materials * 6, -1);
     for (int32_t i = 0; i < n_materials; ++i) {
         const pbr_material& m = materials[i];
         if (m.flags & ~known) return PBR_ERR_INVALID_ARGUMENT;
@@ -64,6 +68,7 @@ int pbr_set_materials(pbr_context* ctx, const pbr_material* materials, int32_t n
             const int32_t t = m.tex[slot_of_bit[b]];
             if (t < 0 || t >= n_textures) return PBR_ERR_INVALID_ARGUMENT;
             r.tex[slot_of_bit[b]] = place[(size_t)t];
+            slot_tex[(size_t)i * 6 + (size_t)slot_of_bit[b]] = t;
         }
     }
     // Repack to RGBA8: one aligned dword per tap whatever the channel count; a gray texture replicates .r.
@@ -84,6 +89,7 @@ int pbr_set_materials(pbr_context* ctx, const pbr_material* materials, int32_t n
     if (const int rc = en.open(stream, "pbr_set_materials stream")) return rc;
     pbr_context::Materials& mt = ctx->mats;
     mt.set = false;
+    ctx->mips.set = false;  // the chains belong to the table they were built from (pbr_generate_mips)
     // The old table and texels may still be read by queued resolves: released after them, in stream order.
     if (const int rc = replace_pair(en, mt.use, recs.data(), sizeof(pbr::MaterialRec) * recs.size(), texels.data(),
                                     sizeof(uint32_t) * texels.size(), "pbr_set_materials"))
@@ -92,21 +98,110 @@ int pbr_set_materials(pbr_context* ctx, const pbr_material* materials, int32_t n
     mt.n_texels = (int64_t)texels.size();
     mt.flags.resize((size_t)n_materials);
     for (int32_t i = 0; i < n_materials; ++i) mt.flags[(size_t)i] = materials[i].flags;
+    mt.place = std::move(place);
+    mt.slot_tex = std::move(slot_tex);
     mt.set = true;
     return PBR_OK;
 }
 
-int pbr_resolve_materials(pbr_context* ctx, const pbr_attributes_soa* at, const pbr_gbuffer_targets* tg, int32_t filter,
-                          void* stream) {
-    if (!ctx || !at || !tg) return PBR_ERR_INVALID_ARGUMENT;
-    if (at->width < 0 || at->height < 0 || at->row_stride < at->width || tg->row_stride < at->width)
-        return PBR_ERR_INVALID_ARGUMENT;
-    if (filter != PBR_FILTER_POINT && filter != PBR_FILTER_LINEAR) return PBR_ERR_INVALID_ARGUMENT;
-    if (tg->coverage && tg->coverage_row_stride < at->width) return PBR_ERR_INVALID_ARGUMENT;
+int pbr_generate_mips(pbr_context* ctx, void* stream) {
+    if (!ctx) return PBR_ERR_INVALID_ARGUMENT;
     Entry en(ctx);
-    if (!ctx->mats.set) return PBR_ERR_NOT_READY;
-    if (at->width == 0 || at->height == 0) return PBR_OK;  // empty frame: nothing is read or written
-    pbr::ResolveArgs a{};
+    const pbr_context::Materials& mt = ctx->mats;
+    if (!mt.set) return PBR_ERR_NOT_READY;
+    // The level table: levels 1 .. L-1 of every texture, texture after texture, W_l = max(1, W_(l-1) >> 1) and H_l alike
+    // down to 1 x 1. The chains hold fewer texels than the upload (at most 2^28), so offsets stay inside 32 bits.
+    const size_t nt = mt.place.size();
+    std::vector<pbr::MaterialTex> levels;
+    std::vector<pbr::MipSlot> chain(nt);
+    int64_t total = 0;
+    int max_levels = 1;
+    for (size_t t = 0; t < nt; ++t) {
+        int32_t w = mt.place[t].w, h = mt.place[t].h;
+        chain[t].first = (uint32_t)levels.size();
+        chain[t].levels = 1;
+        while (w > 1 || h > 1) {
+            w = std::max(1, w >> 1);
+            h = std::max(1, h >> 1);
+            levels.push_back(pbr::MaterialTex{(uint32_t)total, w, h});
+            total += (int64_t)w * h;
+            ++chain[t].levels;
+        }
+        max_levels = std::max(max_levels, (int)chain[t].levels);
+    }
+    // The materials' slots, in MaterialRec::tex order without the opacity map.
+    const size_t nm = (size_t)mt.n;
+    std::vector<pbr::MipSlot> slots(std::max<size_t>(nm * 5, 1), pbr::MipSlot{0u, 1});
+    for (size_t i = 0; i < nm; ++i)
+        for (size_t k = 0; k < 5; ++k)
+            if (const int32_t t = mt.slot_tex[i * 6 + k]; t >= 0) slots[i * 5 + k] = chain[(size_t)t];
+    // One launch per level index over the textures that have it: its table, and the texels before each texture.
+    std::vector<pbr::MipGen> gen;
+    std::vector<size_t> gen_begin((size_t)max_levels + 1, 0);
+    std::vector<uint32_t> gen_texels((size_t)max_levels, 0u);
+    for (int l = 1; l < max_levels; ++l) {
+        gen_begin[(size_t)l] = gen.size();
+        uint32_t first = 0;
+        for (size_t t = 0; t < nt; ++t) {
+            if (chain[t].levels <= l) continue;
+            const pbr::MaterialTex& src = l == 1 ? mt.place[t] : levels[chain[t].first + (size_t)l - 2];
+            const pbr::MaterialTex& dst = levels[chain[t].first + (size_t)l - 1];
+            gen.push_back(pbr::MipGen{src.offset, dst.offset, src.w, src.h, dst.w, dst.h, first, 0u});
+            first += (uint32_t)dst.w * (uint32_t)dst.h;
+        }
+        gen_texels[(size_t)l] = first;
+    }
+    gen_begin[(size_t)max_levels] = gen.size();
+    const size_t off_levels = align_up(sizeof(pbr::MipSlot) * slots.size(), 256);
+    const size_t off_gen = off_levels + align_up(sizeof(pbr::MaterialTex) * levels.size(), 256);
+    const size_t table_bytes = off_gen + std::max<size_t>(sizeof(pbr::MipGen) * gen.size(), 4);
+    const size_t texel_count = (size_t)std::max<int64_t>(total, 1);
+
+    if (const int rc = en.open(stream, "pbr_generate_mips stream")) return rc;
+    pbr_context::Mips& mp = ctx->mips;
+    mp.set = false;
+    // The old chains may still be read by queued resolves: released after them, in stream order. The level launches
+    // read the upload's texels under pbr_resolve_materials's rules.
+    const int rc = replace_buffers(en, mp.use, true, table_bytes, sizeof(uint32_t) * texel_count, "pbr_generate_mips", [&] {
+        char* d = mp.d_tables;
+        hipError_t e = hipMemcpyAsync(d, slots.data(), sizeof(pbr::MipSlot) * slots.size(), hipMemcpyHostToDevice, en.s);
+        if (e == hipSuccess && !levels.empty())
+            e = hipMemcpyAsync(d + off_levels, levels.data(), sizeof(pbr::MaterialTex) * levels.size(),
+                               hipMemcpyHostToDevice, en.s);
+        if (e == hipSuccess && !gen.empty())
+            e = hipMemcpyAsync(d + off_gen, gen.data(), sizeof(pbr::MipGen) * gen.size(), hipMemcpyHostToDevice, en.s);
+        if (e != hipSuccess) return fail_hip(ctx, e, "pbr_generate_mips copy");
+        e = before_read(ctx->mats.use, en.s, en.si);
+        if (e != hipSuccess) return fail_hip(ctx, e, "pbr_generate_mips order");
+        for (int l = 1; l < max_levels; ++l) {
+            pbr::MipGenArgs g{};
+            g.gen = reinterpret_cast<const pbr::MipGen*>(d + off_gen) + gen_begin[(size_t)l];
+            g.n = (int)(gen_begin[(size_t)l + 1] - gen_begin[(size_t)l]);
+            g.n_out = gen_texels[(size_t)l];
+            g.src = l == 1 ? mt.d_texels : mp.d_texels;
+            g.n_src = l == 1 ? mt.n_texels : total;
+            g.dst = mp.d_texels;
+            g.n_dst = total;
+            e = pbr::launch_generate_mip_level(g, en.s);
+            if (e != hipSuccess) return fail_hip(ctx, e, "generate_mip_level_kernel launch", PBR_ERR_LAUNCH);
+        }
+        return after_launch(ctx, en.si, en.s, "pbr_generate_mips record");
+    });
+    if (rc) return rc;
+    mp.d_slots = reinterpret_cast<const pbr::MipSlot*>(mp.d_tables);
+    mp.d_levels = reinterpret_cast<const pbr::MaterialTex*>(mp.d_tables + off_levels);
+    mp.n_levels = (int64_t)levels.size();
+    mp.n_texels = total;
+    mp.set = true;
+    return PBR_OK;
+}
+
+// The argument checks pbr_resolve_materials and pbr_resolve_materials_mip share, and the launch arguments they fill.
+static bool resolve_shape_ok(const pbr_attributes_soa* at, const pbr_gbuffer_targets* tg) {
+    if (at->width < 0 || at->height < 0 || at->row_stride < at->width || tg->row_stride < at->width) return false;
+    return !(tg->coverage && tg->coverage_row_stride < at->width);
+}
+static int resolve_args(pbr_context* ctx, const pbr_attributes_soa* at, const pbr_gbuffer_targets* tg, pbr::ResolveArgs& a) {
     const float* in[14] = {at->pos_w[0],     at->pos_w[1],     at->pos_w[2],       at->normal_w[0],    at->normal_w[1],
                            at->normal_w[2],  at->tangent_w[0], at->tangent_w[1],   at->tangent_w[2],   at->bitangent_w[0],
                            at->bitangent_w[1], at->bitangent_w[2], at->tex_coord[0], at->tex_coord[1]};
@@ -132,6 +227,18 @@ int pbr_resolve_materials(pbr_context* ctx, const pbr_attributes_soa* at, const 
     a.n_materials = ctx->mats.n;
     a.texels = ctx->mats.d_texels;
     a.n_texels = debug_bounds_skew() ? 0 : ctx->mats.n_texels;
+    return PBR_OK;
+}
+
+int pbr_resolve_materials(pbr_context* ctx, const pbr_attributes_soa* at, const pbr_gbuffer_targets* tg, int32_t filter,
+                          void* stream) {
+    if (!ctx || !at || !tg || !resolve_shape_ok(at, tg)) return PBR_ERR_INVALID_ARGUMENT;
+    if (filter != PBR_FILTER_POINT && filter != PBR_FILTER_LINEAR) return PBR_ERR_INVALID_ARGUMENT;
+    Entry en(ctx);
+    if (!ctx->mats.set) return PBR_ERR_NOT_READY;
+    if (at->width == 0 || at->height == 0) return PBR_OK;  // empty frame: nothing is read or written
+    pbr::ResolveArgs a{};
+    if (const int rc = resolve_args(ctx, at, tg, a)) return rc;
     a.linear = filter == PBR_FILTER_LINEAR;
 
     if (const int rc = en.open(stream, "pbr_resolve_materials stream")) return rc;
@@ -144,6 +251,32 @@ int pbr_resolve_materials(pbr_context* ctx, const pbr_attributes_soa* at, const 
     return after_launch(ctx, en.si, en.s, "pbr_resolve_materials record");
 }
 
+int pbr_resolve_materials_mip(pbr_context* ctx, const pbr_attributes_soa* at, const pbr_gbuffer_targets* tg, float lod_bias,
+                              void* stream) {
+    if (!ctx || !at || !tg || !resolve_shape_ok(at, tg) || !std::isfinite(lod_bias)) return PBR_ERR_INVALID_ARGUMENT;
+    Entry en(ctx);
+    const pbr_context::Mips& mp = ctx->mips;
+    if (!ctx->mats.set || !mp.set) return PBR_ERR_NOT_READY;
+    if (at->width == 0 || at->height == 0) return PBR_OK;  // empty frame: nothing is read or written
+    pbr::ResolveMipArgs a{};
+    if (const int rc = resolve_args(ctx, at, tg, a.r)) return rc;
+    a.slots = mp.d_slots;
+    a.levels = mp.d_levels;
+    a.n_levels = mp.n_levels;
+    a.mip_texels = mp.d_texels;
+    a.n_mip_texels = mp.n_texels;
+    a.lod_bias = lod_bias;
+
+    if (const int rc = en.open(stream, "pbr_resolve_materials_mip stream")) return rc;
+    hipError_t e = before_read(ctx->mats.use, en.s, en.si);
+    if (e == hipSuccess) e = before_read(ctx->mips.use, en.s, en.si);
+    if (e != hipSuccess) return fail_hip(ctx, e, "pbr_resolve_materials_mip order");
+    e = pbr::launch_resolve_materials_mip(a, en.s);
+    if (e != hipSuccess) return fail_hip(ctx, e, "resolve_materials_mip_kernel launch", PBR_ERR_LAUNCH);
+    // Not a shading pass, as pbr_resolve_materials.
+    return after_launch(ctx, en.si, en.s, "pbr_resolve_materials_mip record");
+}
+
 }  // extern "C"
 
 // ---- Rasteriser (VS + the fixed-function rasteriser on the device; raster.h) --------------------------
@@ -151,8 +284,6 @@ int pbr_resolve_materials(pbr_context* ctx, const pbr_attributes_soa* at, const 
 namespace {
 
 constexpr int32_t kRasterMaxSide = 32768;  // frame width and height: keeps every block and pixel count inside 32 bits
-
-size_t align_up(size_t n, size_t a) { return (n + a - 1) / a * a; }
 
 // The calling stream's pinned staging with room for `bytes`, free to be written: waits (on the host) for the upload
 // that last read it.

@@ -401,6 +401,15 @@ class ShadingContext:
         pass with ``PBR_FLAG_F0_PLANE``); ``coverage`` is the (H, W) uint8 plane of ``shade_frame``. ``out``: a
         ``GBuffer`` or a ``(GBuffer, coverage)`` pair to write into (an absent opacity or coverage plane is not
         written); default: fresh tensors."""
+        gb, coverage, t = self._resolve_targets(attrs, out)
+        a = attrs.to_c()
+        N.check(self.lib.pbr_resolve_materials(self._h, ctypes.byref(a), ctypes.byref(t), int(filter),
+                                               ctypes.c_void_p(_stream_handle(stream))),
+                "pbr_resolve_materials", self._h)
+        return gb, coverage
+
+    def _resolve_targets(self, attrs: Attributes, out):
+        """``out`` of :meth:`resolve` / :meth:`resolve_mip` as ``(GBuffer, coverage, pbr_gbuffer_targets)``."""
         self._check_device(attrs.planes, attrs.material)
         dev = attrs.planes.device
         if out is None:
@@ -426,10 +435,26 @@ class ShadingContext:
                 raise ValueError("coverage is smaller than the attributes")
             t.coverage = coverage.data_ptr()
             t.coverage_row_stride = coverage.stride(0)
+        return gb, coverage, t
+
+    def generate_mips(self, stream=None) -> None:
+        """Build the mip chains of the current material table's textures on the device (pbr_generate_mips; the
+        MipLevels of the reference's textures, PBRApp.cpp:701, :1171-1178). Call it after every
+        :meth:`set_materials` whose table :meth:`resolve_mip` is to sample; synchronises ``stream``."""
+        N.check(self.lib.pbr_generate_mips(self._h, ctypes.c_void_p(_stream_handle(stream))), "pbr_generate_mips",
+                self._h)
+
+    def resolve_mip(self, attrs: Attributes, lod_bias: float = 0.0, out=None, stream=None):
+        """:meth:`resolve` with the mip-mapped trilinear filter on the five material maps
+        (pbr_resolve_materials_mip): the level of detail of a pixel comes from the differences of its UV
+        inside its 2 x 2 pixel quad, plus ``lod_bias``. Needs :meth:`generate_mips`. A row band of ``attrs`` must start
+        on an even row of the frame and have an even height or end with the frame. Returns what :meth:`resolve`
+        returns."""
+        gb, coverage, t = self._resolve_targets(attrs, out)
         a = attrs.to_c()
-        N.check(self.lib.pbr_resolve_materials(self._h, ctypes.byref(a), ctypes.byref(t), int(filter),
-                                               ctypes.c_void_p(_stream_handle(stream))),
-                "pbr_resolve_materials", self._h)
+        N.check(self.lib.pbr_resolve_materials_mip(self._h, ctypes.byref(a), ctypes.byref(t), float(lod_bias),
+                                                   ctypes.c_void_p(_stream_handle(stream))),
+                "pbr_resolve_materials_mip", self._h)
         return gb, coverage
 
     def set_meshes(self, meshes: Sequence[Mesh], stream=None) -> None:
@@ -611,7 +636,8 @@ class ShadingContext:
         return frame
 
     def draw_transparent(self, draws: Sequence[Draw], view: View, depth: torch.Tensor, frame: torch.Tensor, *,
-                         flags: int = 0, filter: int = N.PBR_FILTER_POINT, max_layers: int = 8, stream=None):
+                         flags: int = 0, filter: int = N.PBR_FILTER_POINT, max_layers: int = 8, stream=None,
+                         mip_lod_bias: Optional[float] = None):
         """The reference's transparent pass (RenderLayer::Transparent, PBRApp.cpp:313-316) over a finished frame:
         layer after layer, :meth:`rasterize_layer` -> :meth:`resolve` -> :meth:`shade` -> :meth:`blend_layer`, until a
         layer is empty or ``max_layers`` layers were blended. ``depth``: the (H, row_stride) float32 depth plane of the
@@ -620,7 +646,10 @@ class ShadingContext:
         :meth:`set_pass` shades every layer (set ``PBR_FLAG_F0_PLANE``, as for any resolved G-buffer). Each layer
         re-runs the vertex transform and the setup and shades the whole band. Returns ``(layers, stopped_on_empty)``:
         how many layers were blended and whether the loop ended on an empty layer (False: ``max_layers`` was reached
-        and more may remain). Synchronises ``stream`` once per layer, to read the layer's counter."""
+        and more may remain). Synchronises ``stream`` once per layer, to read the layer's counter. ``mip_lod_bias``: when
+        not None, every layer goes through :meth:`resolve_mip` with that bias (``filter`` is then not used; needs
+        :meth:`generate_mips`; the view's band must then start on an even row and have an even height or end with the
+        frame)."""
         v = view.to_c()
         rows = max(v.row_end - v.row_begin, 0)
         dev = torch.device("cuda", self.device)
@@ -637,7 +666,10 @@ class ShadingContext:
                                  stream=stream)
             if self.raster_layer_stats(stream)["layer_fragments"] == 0:
                 return k, True
-            self.resolve(attrs, filter, out=(gb, coverage), stream=stream)
+            if mip_lod_bias is None:
+                self.resolve(attrs, filter, out=(gb, coverage), stream=stream)
+            else:
+                self.resolve_mip(attrs, mip_lod_bias, out=(gb, coverage), stream=stream)
             self.shade(gb, shaded, stream=stream)
             self.blend_layer(shaded, gb.opacity, coverage, frame, width=view.width, height=rows, stream=stream)
         return int(max_layers), False

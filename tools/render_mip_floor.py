@@ -1,0 +1,74 @@
+"""Render one minified view twice on the GPU -- a textured floor that recedes to the horizon under one of the committed
+1K tile sets, rasterised, resolved and shaded on the device -- once with the level-0 linear filter
+(pbr_resolve_materials) and once with the mip-mapped trilinear filter (pbr_generate_mips + pbr_resolve_materials_mip,
+DESIGN.md §11), and write both as PNG.
+
+    python tools/render_mip_floor.py [--width 960 --height 540] [--tile 0] [--lod-bias 0]
+                                     [--out-dir build/mip_floor]
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from physically_based_renderer_amd import _native as N, envmap, image_io  # noqa: E402
+from physically_based_renderer_amd import scenes as S  # noqa: E402
+from physically_based_renderer_amd.renderer import Draw, Mesh, PassConstants, ShadingContext  # noqa: E402
+
+
+def floor_mesh(half_width, depth, tiles_per_unit):
+    """A quad on y = 0 from z = 0 to z = depth; its UV repeats `tiles_per_unit` times per world unit."""
+    x, z = half_width, depth
+    v = np.zeros((4, 14), np.float32)
+    v[:, 0:3] = [(-x, 0, 0), (x, 0, 0), (x, 0, z), (-x, 0, z)]
+    v[:, 3:6] = (0, 1, 0)
+    v[:, 6:9] = (1, 0, 0)
+    v[:, 9:12] = (0, 0, -1)
+    v[:, 12] = (v[:, 0] + x) * tiles_per_unit
+    v[:, 13] = (z - v[:, 2]) * tiles_per_unit
+    return Mesh(v, np.array([0, 3, 2, 0, 2, 1], np.uint32))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--width", type=int, default=960)
+    ap.add_argument("--height", type=int, default=540)
+    ap.add_argument("--tile", type=int, default=0, help="which of the committed 1K tile sets covers the floor")
+    ap.add_argument("--lod-bias", type=float, default=0.0)
+    ap.add_argument("--out-dir", default=os.path.join(ROOT, "build", "mip_floor"))
+    a = ap.parse_args()
+    cfg = S.CONFIGS[4]
+    mats, texs = S.scene_materials(cfg)
+    view = S.look_at_view((0.0, 1.2, -1.0), (0.0, 0.9, 6.0), float(np.pi / 3), a.width, a.height, far=400.0)
+    lights = np.zeros((2, 12), np.float32)
+    lights[:, 0:3] = [(2.0, 1.9, 1.7), (0.5, 0.6, 0.8)]
+    lights[:, 4:7] = [(0.3, -0.8, 0.5), (-0.6, -0.5, -0.2)]
+    pc = PassConstants(eye_pos_w=view.eye, num_dir_lights=2, lights_array=lights, ambient_light=(0.08, 0.08, 0.08),
+                       flags=N.PBR_FLAG_F0_PLANE)
+    os.makedirs(a.out_dir, exist_ok=True)
+    with ShadingContext(0) as ctx:
+        ctx.set_meshes([floor_mesh(40.0, 300.0, 0.5)])
+        ctx.set_materials(mats, texs)
+        ctx.generate_mips()
+        ctx.set_pass(pc)
+        ctx.set_sky_map(envmap.procedural_sky_rgba16(512, 256))
+        at = ctx.rasterize([Draw(mesh=0, material=a.tile, cull=1)], view)
+        for name, resolve in (("linear", lambda: ctx.resolve(at, N.PBR_FILTER_LINEAR)),
+                              ("trilinear", lambda: ctx.resolve_mip(at, a.lod_bias))):
+            gb, cov = resolve()
+            img = ctx.shade_frame(gb, coverage=cov, fmt=N.PBR_OUTPUT_RGBA8_UNORM)
+            torch.cuda.synchronize()
+            out = os.path.join(a.out_dir, f"mip_floor_{name}.png")
+            image_io.write_png_rgba8(out, img)
+            # how much neighbouring pixels differ in the far half of the floor: what shimmers when the camera moves
+            far = img[: a.height // 2 + a.height // 8].float()
+            print(f"{name}: {a.width}x{a.height} floor covered {float((cov != 0).float().mean()):.3f}, mean |dx| of the "
+                  f"upper rows' RGB {float((far[:, 1:, :3] - far[:, :-1, :3]).abs().mean()):.2f} / 255 -> {os.path.basename(out)}")
+
+
+if __name__ == "__main__":
+    main()

@@ -6,7 +6,11 @@ to the same device G-buffer and against the box's streaming rate, in one process
       123 B per pixel; texel fetches are not counted);
   (b) the host route: pbr_gbuffer_fill on 16 threads + GBuffer.from_host (15 fp32 planes over PCIe), host clock
       around work that ends in a device synchronise;
-  (c) a device-to-device copy moving (a)'s byte count (half read, half written): the streaming yardstick.
+  (c) a device-to-device copy moving (a)'s byte count (half read, half written): the streaming yardstick;
+  (d) the trilinear resolve (pbr_resolve_materials_mip) beside (a)'s linear leg, the yardstick of this leg: (i) lod 0
+      everywhere (a bias of -64 clamps every sample to level 0: the magnified case, one bilinear per sample), the
+      scene's own footprints (bias 0), (ii) bias 1.5 (every sample between two levels: two bilinears); and
+      pbr_generate_mips on the scene's textures (host clock: the call synchronises its stream).
 
     python tools/resolve_bench.py [--width 3840 --height 2160] [--steps 50] [--log profiles/r09/resolve_bench.log]
 
@@ -104,6 +108,28 @@ def main():
             r = event_ms(lambda: ctx.resolve(attrs, filt, out=out), a.steps)
             r.update(leg="a_resolve_" + name, gb_per_s=total / (r["median_ms"] * 1e-3) / 1e9)
             res[name] = r
+            emit(r)
+        # (d) the trilinear resolve and the chain generation
+        gen = []
+        for _ in range(7):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            ctx.generate_mips()
+            gen.append((time.perf_counter() - t0) * 1e3)
+        gen.sort()
+        mats, texs = S.scene_materials(cfg)
+        emit({"leg": "d_generate_mips", "median_ms": gen[len(gen) // 2], "min_ms": gen[0], "max_ms": gen[-1],
+              "textures": len(texs), "level0_texels": int(sum(t.shape[0] * t.shape[1] for t in texs))})
+        same = torch.equal(ctx.resolve_mip(attrs, -64.0)[0].planes.view(torch.int32),
+                           ctx.resolve(attrs, N.PBR_FILTER_LINEAR)[0].planes.view(torch.int32))
+        emit({"check": "trilinear at lod 0 == linear planes", "bit_identical": bool(same)})
+        if not same:
+            sys.exit("resolve_bench: the trilinear resolve at lod 0 differs from the linear filter")
+        for name, bias in (("lod0", -64.0), ("bias0", 0.0), ("bias1.5", 1.5)):
+            out = ctx.resolve_mip(attrs, bias)
+            r = event_ms(lambda: ctx.resolve_mip(attrs, bias, out=out), a.steps)
+            r.update(leg="d_resolve_mip_" + name, lod_bias=bias, gb_per_s=total / (r["median_ms"] * 1e-3) / 1e9,
+                     over_linear=r["median_ms"] / res["linear"]["median_ms"])
             emit(r)
         # (c) device-to-device copy moving the same bytes (half read, half written)
         src = torch.empty(total // 2, dtype=torch.uint8, device=dev)
