@@ -341,9 +341,9 @@ int pbr_resolve_materials(pbr_context* ctx, const pbr_attributes_soa* attrs, con
 
 /* ---- Mip chains and the trilinear filter (additive: PBR_ABI_VERSION stays 9, detect by symbol) ----
  * The reference samples every material map with g_SamAnisotropicWrap over texture->Resource->GetDesc().MipLevels
- * levels (PBRApp.cpp:701, :1171-1178; Default.hlsl:80-105). Anisotropy stays parity-unpinned; the isotropic trilinear
- * filter over chains this library builds itself is pinned bit for bit ("Mip chains and the trilinear
- * filter", which fixes every operation).
+ * levels (PBRApp.cpp:701, :1171-1178; Default.hlsl:80-105). The isotropic trilinear filter over chains this library
+ * builds itself is pinned bit for bit ("Mip chains and the trilinear filter", which fixes every
+ * operation); the anisotropic filter over the same chains is pbr_resolve_materials_aniso below, pinned the same way.
  *
  * pbr_generate_mips builds the chains of every texture of the current material table on the device, the counterpart of
  * the mips a DDS carries or a loader generates. Level 0 is the uploaded texture; level l >= 1 is
@@ -371,6 +371,32 @@ int pbr_generate_mips(pbr_context* ctx, void* stream);
  * anew; PBR_ERR_INVALID_ARGUMENT also for a lod_bias that is NaN or infinite. */
 int pbr_resolve_materials_mip(pbr_context* ctx, const pbr_attributes_soa* attrs, const pbr_gbuffer_targets* targets,
                               float lod_bias, void* stream);
+
+/* ---- Anisotropic filter (additive: PBR_ABI_VERSION stays 9, detect by symbol) ----
+ * pbr_resolve_materials_mip with the anisotropic filter on the five material maps (the reference's sampler is
+ * D3D12_FILTER_ANISOTROPIC with maxAnisotropy = 8, PBRApp.cpp:1171-1178); DESIGN.md §11, "Anisotropic filter", fixes
+ * every operation. Partners, validity, dudx, dvdx, dudy, dvdy, quad alignment and the band rule are
+ * pbr_resolve_materials_mip's; the PBR_MAT_ALPHA_TEST opacity stays the level-0 point-wrap tap. Per sampled texture of
+ * W x H texels and L levels, with M = max_anisotropy, in fp32, every operation rounded once:
+ *   rx = (dudx W)^2 + (dvdx H)^2, ry = (dudy W)^2 + (dvdy H)^2; ymajor = ry > rx (false for NaN);
+ *   pmax2, pmin2 = the larger and the smaller of the two; (du, dv) = (dudy, dvdy) when ymajor, else (dudx, dvdx).
+ *   N = 1; for k = 1 .. M-1 ascending: if pmax2 > (float)(k k) * pmin2 then N = k + 1 -- the smallest n with
+ *   pmax2 <= n^2 pmin2, at most M; NaN gives 1, both lengths zero give 1, a zero minor axis under a non-zero major
+ *   one gives M.
+ *   r2 = N > 1 ? pmax2 / (float)(N N) : pmax2; lod, the levels l0 and l1 and the fraction f from r2 as in
+ *   pbr_resolve_materials_mip.
+ *   Taps: N == 1: (u, v) itself; else for i = 0 .. N-1: t_i = (float)(2 i + 1 - N) / (float)(2 N),
+ *   (u + t_i * du, v + t_i * dv).
+ *   Per level l of (l0, l1): s_l = PBR_FILTER_LINEAR's bilinear of level l at tap 0, plus tap 1, ..., plus tap N-1, in
+ *   that order; c_l = N > 1 ? s_l / (float)N : s_l. The sample is c_l0 + f * (c_l1 - c_l0); level l1 is not read when
+ *   f == 0.
+ * With max_anisotropy = 1, and at any pixel and texture where N == 1, the result is pbr_resolve_materials_mip's bit for
+ * bit. The major axis is the longer of the two screen-axis footprints (the form of GL's anisotropic-filter extension),
+ * not the major axis of the footprint ellipse.
+ * PBR_ERR_INVALID_ARGUMENT for max_anisotropy outside 1 .. 16 (D3D12's range) and for a lod_bias that is NaN or
+ * infinite; PBR_ERR_NOT_READY as pbr_resolve_materials_mip. */
+int pbr_resolve_materials_aniso(pbr_context* ctx, const pbr_attributes_soa* attrs, const pbr_gbuffer_targets* targets,
+                                float lod_bias, int32_t max_anisotropy, void* stream);
 
 /* ---- Device rasteriser: indexed triangle meshes -> interpolated attributes ----------------------
  * VS (Default.hlsl:22-45) and the fixed-function rasteriser behind DrawIndexedInstanced (PBRApp.cpp:1133) under the

@@ -392,6 +392,23 @@ class ShadingContext {
         t.coverage_row_stride = coverage_row_stride;
         Check(pbr_resolve_materials_mip(ctx_, &attrs, &t, lod_bias, stream), "pbr_resolve_materials_mip");
     }
+    // ResolveMaterialsMip with the anisotropic filter (pbr_resolve_materials_aniso; the reference's sampler has
+    // maxAnisotropy 8, PBRApp.cpp:1171-1178): up to `max_anisotropy` (1 .. 16) taps along the longer footprint axis.
+    void ResolveMaterialsAniso(const pbr_attributes_soa& attrs, DeviceGBuffer& gb, int32_t row_begin,
+                               int32_t max_anisotropy = 8, float lod_bias = 0.0f, float* opacity = nullptr,
+                               uint8_t* coverage = nullptr, int64_t coverage_row_stride = 0,
+                               hipStream_t stream = nullptr) {
+        pbr_gbuffer_targets t;
+        std::memset(&t, 0, sizeof t);
+        const size_t off = static_cast<size_t>(row_begin) * gb.row_stride();
+        for (int i = 0; i < DeviceGBuffer::kPlanes; ++i) t.planes[i] = gb.plane(i) + off;
+        t.opacity = opacity;
+        t.coverage = coverage;
+        t.row_stride = gb.row_stride();
+        t.coverage_row_stride = coverage_row_stride;
+        Check(pbr_resolve_materials_aniso(ctx_, &attrs, &t, lod_bias, max_anisotropy, stream),
+              "pbr_resolve_materials_aniso");
+    }
 
     // The meshes Rasterize draws from (BuildShapeGeometry's vertex / index buffer uploads): host data, reusable on
     // return.

@@ -348,6 +348,9 @@ SIGNATURES = {
     "pbr_generate_mips": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "pbr_resolve_materials_mip": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(AttributesSoA),
                                                  ctypes.POINTER(GBufferTargets), ctypes.c_float, ctypes.c_void_p]),
+    "pbr_resolve_materials_aniso": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(AttributesSoA),
+                                                   ctypes.POINTER(GBufferTargets), ctypes.c_float, ctypes.c_int32,
+                                                   ctypes.c_void_p]),
     "pbr_set_meshes": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(MeshDesc), ctypes.c_int32, ctypes.c_void_p]),
     "pbr_rasterize": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(DrawDesc), ctypes.c_int32,
                                      ctypes.POINTER(RasterView), ctypes.POINTER(RasterTargets), ctypes.c_void_p]),

@@ -87,6 +87,14 @@ struct ResolveMipArgs {
 };
 hipError_t launch_resolve_materials_mip(const ResolveMipArgs& a, hipStream_t stream);
 
+// ---- The anisotropic resolve (material_resolve.h; pbr_resolve_materials_aniso) -----------------------------------
+// The trilinear call's arguments, unchanged, and the largest tap count of a sample.
+struct ResolveAnisoArgs {
+    ResolveMipArgs m;
+    int32_t max_aniso;  // 1 .. 16
+};
+hipError_t launch_resolve_materials_aniso(const ResolveAnisoArgs& a, hipStream_t stream);
+
 // ---- Rasteriser (raster.h; pbr_rasterize) ---------------------------------------------------------
 // One draw on the device: its constants and where its data is.
 struct RasterDraw {

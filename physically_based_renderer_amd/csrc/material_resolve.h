@@ -24,6 +24,11 @@
 // lane and record paths as resolve_materials_kernel, with the level of detail of each sampled texture taken from the
 // differences of u and v inside the 2 x 2 pixel quad a wave holds: across the lane's own pair, and across lanes L and
 // L ^ 32 (the rows y and y ^ 1) through one half-wave swap per value.
+//
+// The anisotropic filter (pbr_resolve_materials_aniso; the reference's sampler is D3D12_FILTER_ANISOTROPIC with
+// maxAnisotropy 8, PBRApp.cpp:1171-1178): resolve_materials_aniso_kernel is the trilinear kernel around another sampler:
+// the same footprints give a tap count per texture, the level comes from the shorter footprint axis, and the taps along
+// the longer one are fetched in a loop.
 #pragma once
 
 #include "pbr_device_math.h"
@@ -231,6 +236,98 @@ __device__ __forceinline__ void quad_footprints(const PixelIn& p0, const PixelIn
 // The sampler of a pixel with material `id` (wave-uniform or per lane) and footprint `d`.
 __device__ __forceinline__ Trilinear trilinear(const ResolveMipArgs& a, uint32_t id, const Footprint& d) {
     return {a, a.slots + PBR_BOUNDS((int64_t)id * 5, (int64_t)a.r.n_materials * 5, kBoundsTexel), d};
+}
+
+// The anisotropic filter over a material's mip chains ("Anisotropic filter"): the sampler of
+// resolve_materials_aniso_kernel. The level comes from the shorter of the two screen-axis footprints, N <= max_aniso
+// bilinear taps are spread along the longer one, averaged per level, and the two levels are mixed once. The level loop
+// and the tap loop are real loops with per-lane trip counts (1 or 2, and 1 .. 16): they run inside divergent code and
+// hold no cross-lane operation; a fetch inlines one bilinear, not one per tap and level.
+struct Anisotropic {
+    const ResolveAnisoArgs& a;
+    const MipSlot* slots;
+    Footprint d;
+    template <int NCH>
+    __device__ __forceinline__ void fetch(const uint32_t*, int64_t, const MaterialTex& t, int slot, float u, float v,
+                                          float* out) const {
+        const ResolveMipArgs& ma = a.m;
+        const MipSlot chain = slots[slot];
+        const int last = chain.levels - 1;
+        const float ax = d.dudx * (float)t.w, ay = d.dvdx * (float)t.h;
+        const float bx = d.dudy * (float)t.w, by = d.dvdy * (float)t.h;
+        const float rx = ax * ax + ay * ay, ry = bx * bx + by * by;
+        const bool ymajor = ry > rx;  // false for NaN
+        const float pmax2 = ymajor ? ry : rx, pmin2 = ymajor ? rx : ry;
+        const float du = ymajor ? d.dudy : d.dudx, dv = ymajor ? d.dvdy : d.dvdx;  // UV units
+        // The smallest n with pmax2 <= n^2 pmin2, at most max_aniso: NaN gives 1, a zero minor axis under a non-zero
+        // major one gives max_aniso. A compare and a select per step; the trip count is wave-uniform (a kernel
+        // argument), so max_aniso = 1 pays for no step.
+        int n = 1;
+#pragma unroll 1
+        for (int k = 1; k < a.max_aniso; ++k)
+            if (pmax2 > (float)(k * k) * pmin2) n = k + 1;
+        const bool many = n > 1;  // a lane with one tap takes none of the divisions below
+        const float fn = (float)n;
+        float r2 = pmax2;
+        if (many) r2 = pmax2 / (float)(n * n);
+        float base = 0.0f;
+        if (r2 > 1.0f) {  // false for NaN; the piecewise-linear log2: exponent plus mantissa fraction
+            const uint32_t b = __float_as_uint(r2);
+            const float l2 = (float)((int)(b >> 23) - 127) + (float)(b & 0x7FFFFFu) * 0x1p-23f;
+            base = 0.5f * l2;
+        }
+        float lod = base + ma.lod_bias;
+        if (lod < 0.0f) lod = 0.0f;
+        if (lod > (float)last) lod = (float)last;
+        const int l0 = (int)floorf(lod);
+        const float f = lod - (float)l0;
+        const int l1 = l0 + 1 < last ? l0 + 1 : last;
+        const int n_pass = f != 0.0f ? 2 : 1;  // f == 0: c0 + 0 * (c1 - c0) has c0's bits
+        const float two_n = (float)(2 * n);
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) out[c] = 0.0f;
+#pragma unroll 1
+        for (int pass = 0; pass < n_pass; ++pass) {
+            // The level's texels and size, once per level: level 0 in the upload's buffer, the others in the chains'.
+            const int l = pass == 0 ? l0 : l1;
+            const uint32_t* texels = ma.r.texels;
+            int64_t n_texels = ma.r.n_texels;
+            MaterialTex tl = t;
+            if (l != 0) {
+                tl = ma.levels[PBR_BOUNDS((int64_t)chain.first + (l - 1), ma.n_levels, kBoundsTexel)];
+                texels = ma.mip_texels;
+                n_texels = ma.n_mip_texels;
+            }
+            float s[NCH];
+#pragma unroll
+            for (int c = 0; c < NCH; ++c) s[c] = 0.0f;
+#pragma unroll 1
+            for (int i = 0; i < n; ++i) {
+                // Centred on (u, v), evenly spaced, spanning (N - 1) / N of the major axis; N == 1: (u, v) itself.
+                float ui = u, vi = v;
+                if (many) {
+                    const float ti = (float)(2 * i + 1 - n) / two_n;
+                    ui = u + ti * du;
+                    vi = v + ti * dv;
+                }
+                float b[NCH];
+                sample<NCH, true>(texels, n_texels, tl, ui, vi, b);
+#pragma unroll
+                for (int c = 0; c < NCH; ++c) s[c] = i == 0 ? b[c] : s[c] + b[c];
+            }
+            if (many) {
+#pragma unroll
+                for (int c = 0; c < NCH; ++c) s[c] = s[c] / fn;
+            }
+#pragma unroll
+            for (int c = 0; c < NCH; ++c) out[c] = pass == 0 ? s[c] : hlerp(out[c], s[c], f);
+        }
+    }
+};
+
+// The sampler of a pixel with material `id` (wave-uniform or per lane) and footprint `d`.
+__device__ __forceinline__ Anisotropic anisotropic(const ResolveAnisoArgs& a, uint32_t id, const Footprint& d) {
+    return {a, a.m.slots + PBR_BOUNDS((int64_t)id * 5, (int64_t)a.m.r.n_materials * 5, kBoundsTexel), d};
 }
 
 }  // namespace resolve
@@ -451,6 +548,121 @@ __global__ __launch_bounds__(256) void resolve_materials_mip_kernel(const Resolv
     }
 }
 
+// pbr_resolve_materials_aniso: resolve_materials_mip_kernel with the anisotropic sampler. Written out again, not
+// shared through a template, so that the older kernels' instruction streams stay what they were; the footprint
+// exchange sits where it does there, ahead of every divergent branch, and is the only cross-lane traffic besides the
+// one-material ballot. Left to itself the allocator takes 168 VGPRs, the most that three waves per SIMD allow (and took
+// 172, two waves, for an earlier form of the sampler); the kernel names the three waves it is meant to keep -- the
+// trilinear kernel's occupancy -- and gets 163 VGPRs without scratch.
+template <bool VEC>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3)))
+void resolve_materials_aniso_kernel(const ResolveAnisoArgs aa) {
+    using namespace resolve;
+    const ResolveArgs& a = aa.m.r;
+    const int x = (int)blockIdx.x * kResolveTileW + (int)(threadIdx.x & 31u) * 2;
+    const int y = (int)blockIdx.y * kResolveTileH + (int)(threadIdx.x >> 5);
+    const bool in0 = y < a.height && x < a.width, in1 = y < a.height && x + 1 < a.width;
+    const bool pair = VEC && in1;  // both pixels through one 8-byte access per plane
+    const int64_t ii = (int64_t)y * a.in_stride + x;
+    const uint32_t n_mat = (uint32_t)a.n_materials;
+
+    uint32_t id0 = 0xFFFFu, id1 = 0xFFFFu;
+    PixelIn p0{}, p1{};
+    if (pair) {
+        const int64_t i = PBR_BOUNDS_PIXEL(ii, a.width, a.height, a.in_stride, 2, kBoundsGBuffer);
+        const uint32_t two = *reinterpret_cast<const uint32_t*>(a.material + i);
+        id0 = two & 0xFFFFu;
+        id1 = two >> 16;
+        float* q0 = p0.a;
+        float* q1 = p1.a;
+#pragma unroll
+        for (int k = 0; k < 14; ++k) {
+            const float2 v = *reinterpret_cast<const float2*>(a.attr[k] + i);
+            q0[k] = v.x;
+            q1[k] = v.y;
+        }
+    } else {
+        if (in0) {
+            const int64_t i = PBR_BOUNDS_PIXEL(ii, a.width, a.height, a.in_stride, 1, kBoundsGBuffer);
+            id0 = a.material[i];
+            float* q0 = p0.a;
+#pragma unroll
+            for (int k = 0; k < 14; ++k) q0[k] = a.attr[k][i];
+        }
+        if (in1) {
+            const int64_t i = PBR_BOUNDS_PIXEL(ii + 1, a.width, a.height, a.in_stride, 1, kBoundsGBuffer);
+            id1 = a.material[i];
+            float* q1 = p1.a;
+#pragma unroll
+            for (int k = 0; k < 14; ++k) q1[k] = a.attr[k][i];
+        }
+    }
+    const bool g0 = in0 && id0 < n_mat, g1 = in1 && id1 < n_mat;
+    // Every lane of the wave gets here together (pixels outside the frame and background pixels included), ahead of
+    // the divergent branches below: the wave's two rows exchange u, v and the ids.
+    Footprint d[2];
+    quad_footprints(p0, p1, id0, id1, d);
+
+    PixelOut o0, o1;
+    background_pixel(p0, o0);
+    background_pixel(p1, o1);
+    // One material for the whole wave? Every geometry pixel's id against the first geometry lane's.
+    const uint32_t key = g0 ? id0 : g1 ? id1 : 0xFFFFFFFFu;
+    const uint64_t any = __ballot(key != 0xFFFFFFFFu);
+    if (any != 0) {
+        const int lead = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(any));
+        const uint32_t first = (uint32_t)__builtin_amdgcn_readlane((int)key, lead);
+        const bool differs = (g0 && id0 != first) || (g1 && id1 != first);
+        if (__ballot(differs) == 0) {
+            const MaterialRec& m = a.table[PBR_BOUNDS((int64_t)first, (int64_t)n_mat, kBoundsTexel)];
+            if (g0) resolve_pixel(m, a.texels, a.n_texels, p0, o0, anisotropic(aa, first, d[0]));
+            if (g1) resolve_pixel(m, a.texels, a.n_texels, p1, o1, anisotropic(aa, first, d[1]));
+        } else {
+            if (g0)
+                resolve_pixel(a.table[PBR_BOUNDS((int64_t)id0, (int64_t)n_mat, kBoundsTexel)], a.texels, a.n_texels,
+                              p0, o0, anisotropic(aa, id0, d[0]));
+            if (g1)
+                resolve_pixel(a.table[PBR_BOUNDS((int64_t)id1, (int64_t)n_mat, kBoundsTexel)], a.texels, a.n_texels,
+                              p1, o1, anisotropic(aa, id1, d[1]));
+        }
+    }
+
+    // pbr_gbuffer_soa order: pos xyz, normal xyz, albedo rgb, metallic, roughness, ao, f0 rgb
+    const float v0[15] = {p0.a[0], p0.a[1], p0.a[2], o0.n[0], o0.n[1], o0.n[2], o0.alb[0], o0.alb[1],
+                          o0.alb[2], o0.metal, o0.rough, 1.0f, o0.f0[0], o0.f0[1], o0.f0[2]};
+    const float v1[15] = {p1.a[0], p1.a[1], p1.a[2], o1.n[0], o1.n[1], o1.n[2], o1.alb[0], o1.alb[1],
+                          o1.alb[2], o1.metal, o1.rough, 1.0f, o1.f0[0], o1.f0[1], o1.f0[2]};
+    const int64_t oi = (int64_t)y * a.out_stride + x, ci = (int64_t)y * a.cov_stride + x;
+    if (pair) {
+        const int64_t i = PBR_BOUNDS_PIXEL(oi, a.width, a.height, a.out_stride, 2, kBoundsOutput);
+#pragma unroll
+        for (int k = 0; k < 15; ++k) *reinterpret_cast<float2*>(a.plane[k] + i) = make_float2(v0[k], v1[k]);
+        if (a.opacity) *reinterpret_cast<float2*>(a.opacity + i) = make_float2(o0.opacity, o1.opacity);
+        if (a.coverage)
+            *reinterpret_cast<uint16_t*>(a.coverage +
+                                         PBR_BOUNDS_PIXEL(ci, a.width, a.height, a.cov_stride, 2, kBoundsCoverage)) =
+                (uint16_t)(o0.cov | (o1.cov << 8));
+    } else {
+        if (in0) {
+            const int64_t i = PBR_BOUNDS_PIXEL(oi, a.width, a.height, a.out_stride, 1, kBoundsOutput);
+#pragma unroll
+            for (int k = 0; k < 15; ++k) a.plane[k][i] = v0[k];
+            if (a.opacity) a.opacity[i] = o0.opacity;
+            if (a.coverage)
+                a.coverage[PBR_BOUNDS_PIXEL(ci, a.width, a.height, a.cov_stride, 1, kBoundsCoverage)] = (uint8_t)o0.cov;
+        }
+        if (in1) {
+            const int64_t i = PBR_BOUNDS_PIXEL(oi + 1, a.width, a.height, a.out_stride, 1, kBoundsOutput);
+#pragma unroll
+            for (int k = 0; k < 15; ++k) a.plane[k][i] = v1[k];
+            if (a.opacity) a.opacity[i] = o1.opacity;
+            if (a.coverage)
+                a.coverage[PBR_BOUNDS_PIXEL(ci + 1, a.width, a.height, a.cov_stride, 1, kBoundsCoverage)] =
+                    (uint8_t)o1.cov;
+        }
+    }
+}
+
 // One level of every chain that has it (pbr_generate_mips): a lane per texel of the level, its texture
 // found from the prefix of texel counts; each byte channel is (a + b + c + d + 2) >> 2 of the 2 x 2 texels of the
 // level before, columns and rows clamped to its last. Even and odd bytes are summed in 16-bit fields of two dwords
@@ -510,6 +722,17 @@ hipError_t launch_resolve_materials(const ResolveArgs& a, hipStream_t stream) {
         else
             hipLaunchKernelGGL((resolve_materials_kernel<false, false>), grid, dim3(256), 0, stream, a);
     }
+    return hipGetLastError();
+}
+
+hipError_t launch_resolve_materials_aniso(const ResolveAnisoArgs& a, hipStream_t stream) {
+    const ResolveArgs& r = a.m.r;
+    if (r.width <= 0 || r.height <= 0) return hipSuccess;
+    const dim3 grid((r.width + kResolveTileW - 1) / kResolveTileW, (r.height + kResolveTileH - 1) / kResolveTileH);
+    if (r.vec)
+        hipLaunchKernelGGL((resolve_materials_aniso_kernel<true>), grid, dim3(256), 0, stream, a);
+    else
+        hipLaunchKernelGGL((resolve_materials_aniso_kernel<false>), grid, dim3(256), 0, stream, a);
     return hipGetLastError();
 }
 

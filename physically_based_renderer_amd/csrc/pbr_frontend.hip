@@ -251,8 +251,13 @@ int pbr_resolve_materials(pbr_context* ctx, const pbr_attributes_soa* at, const 
     return after_launch(ctx, en.si, en.s, "pbr_resolve_materials record");
 }
 
-int pbr_resolve_materials_mip(pbr_context* ctx, const pbr_attributes_soa* at, const pbr_gbuffer_targets* tg, float lod_bias,
-                              void* stream) {
+}  // extern "C"
+
+// pbr_resolve_materials_mip and pbr_resolve_materials_aniso: one validation, one bookkeeping of the two resources read
+// (the material table with its texels, the chains); `launch` starts the call's kernel on the filled arguments.
+template <class Launch>
+static int resolve_mip_call(pbr_context* ctx, const pbr_attributes_soa* at, const pbr_gbuffer_targets* tg, float lod_bias,
+                            void* stream, const char* call, const char* kernel, Launch launch) {
     if (!ctx || !at || !tg || !resolve_shape_ok(at, tg) || !std::isfinite(lod_bias)) return PBR_ERR_INVALID_ARGUMENT;
     Entry en(ctx);
     const pbr_context::Mips& mp = ctx->mips;
@@ -267,14 +272,32 @@ int pbr_resolve_materials_mip(pbr_context* ctx, const pbr_attributes_soa* at, co
     a.n_mip_texels = mp.n_texels;
     a.lod_bias = lod_bias;
 
-    if (const int rc = en.open(stream, "pbr_resolve_materials_mip stream")) return rc;
+    const std::string name(call);
+    if (const int rc = en.open(stream, (name + " stream").c_str())) return rc;
     hipError_t e = before_read(ctx->mats.use, en.s, en.si);
     if (e == hipSuccess) e = before_read(ctx->mips.use, en.s, en.si);
-    if (e != hipSuccess) return fail_hip(ctx, e, "pbr_resolve_materials_mip order");
-    e = pbr::launch_resolve_materials_mip(a, en.s);
-    if (e != hipSuccess) return fail_hip(ctx, e, "resolve_materials_mip_kernel launch", PBR_ERR_LAUNCH);
+    if (e != hipSuccess) return fail_hip(ctx, e, (name + " order").c_str());
+    e = launch(a, en.s);
+    if (e != hipSuccess) return fail_hip(ctx, e, (std::string(kernel) + " launch").c_str(), PBR_ERR_LAUNCH);
     // Not a shading pass, as pbr_resolve_materials.
-    return after_launch(ctx, en.si, en.s, "pbr_resolve_materials_mip record");
+    return after_launch(ctx, en.si, en.s, (name + " record").c_str());
+}
+
+extern "C" {
+
+int pbr_resolve_materials_mip(pbr_context* ctx, const pbr_attributes_soa* at, const pbr_gbuffer_targets* tg, float lod_bias,
+                              void* stream) {
+    return resolve_mip_call(ctx, at, tg, lod_bias, stream, "pbr_resolve_materials_mip", "resolve_materials_mip_kernel",
+                            [](const pbr::ResolveMipArgs& a, hipStream_t s) { return pbr::launch_resolve_materials_mip(a, s); });
+}
+
+int pbr_resolve_materials_aniso(pbr_context* ctx, const pbr_attributes_soa* at, const pbr_gbuffer_targets* tg, float lod_bias,
+                                int32_t max_anisotropy, void* stream) {
+    if (max_anisotropy < 1 || max_anisotropy > 16) return PBR_ERR_INVALID_ARGUMENT;  // D3D12's MaxAnisotropy range
+    return resolve_mip_call(ctx, at, tg, lod_bias, stream, "pbr_resolve_materials_aniso", "resolve_materials_aniso_kernel",
+                            [max_anisotropy](const pbr::ResolveMipArgs& a, hipStream_t s) {
+                                return pbr::launch_resolve_materials_aniso(pbr::ResolveAnisoArgs{a, max_anisotropy}, s);
+                            });
 }
 
 }  // extern "C"

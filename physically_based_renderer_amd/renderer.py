@@ -457,6 +457,19 @@ class ShadingContext:
                 "pbr_resolve_materials_mip", self._h)
         return gb, coverage
 
+    def resolve_aniso(self, attrs: Attributes, max_anisotropy: int = 8, lod_bias: float = 0.0, out=None, stream=None):
+        """:meth:`resolve_mip` with the anisotropic filter on the five material maps (pbr_resolve_materials_aniso;
+        DESIGN.md §11; the reference's sampler has maxAnisotropy 8): per texture, up to ``max_anisotropy`` (1 .. 16)
+        bilinear taps along the longer of the pixel's two footprint axes, at the level of detail of the shorter one.
+        With ``max_anisotropy`` 1 it is :meth:`resolve_mip` bit for bit. Needs :meth:`generate_mips`; the band rule is
+        :meth:`resolve_mip`'s. Returns what :meth:`resolve` returns."""
+        gb, coverage, t = self._resolve_targets(attrs, out)
+        a = attrs.to_c()
+        N.check(self.lib.pbr_resolve_materials_aniso(self._h, ctypes.byref(a), ctypes.byref(t), float(lod_bias),
+                                                     int(max_anisotropy), ctypes.c_void_p(_stream_handle(stream))),
+                "pbr_resolve_materials_aniso", self._h)
+        return gb, coverage
+
     def set_meshes(self, meshes: Sequence[Mesh], stream=None) -> None:
         """Upload the meshes :meth:`rasterize` draws from (pbr_set_meshes; the vertex / index buffer uploads of
         BuildShapeGeometry). An index outside its mesh raises ``PbrError(PBR_ERR_INVALID_ARGUMENT)``."""
@@ -637,7 +650,7 @@ class ShadingContext:
 
     def draw_transparent(self, draws: Sequence[Draw], view: View, depth: torch.Tensor, frame: torch.Tensor, *,
                          flags: int = 0, filter: int = N.PBR_FILTER_POINT, max_layers: int = 8, stream=None,
-                         mip_lod_bias: Optional[float] = None):
+                         mip_lod_bias: Optional[float] = None, max_anisotropy: Optional[int] = None):
         """The reference's transparent pass (RenderLayer::Transparent, PBRApp.cpp:313-316) over a finished frame:
         layer after layer, :meth:`rasterize_layer` -> :meth:`resolve` -> :meth:`shade` -> :meth:`blend_layer`, until a
         layer is empty or ``max_layers`` layers were blended. ``depth``: the (H, row_stride) float32 depth plane of the
@@ -649,7 +662,8 @@ class ShadingContext:
         and more may remain). Synchronises ``stream`` once per layer, to read the layer's counter. ``mip_lod_bias``: when
         not None, every layer goes through :meth:`resolve_mip` with that bias (``filter`` is then not used; needs
         :meth:`generate_mips`; the view's band must then start on an even row and have an even height or end with the
-        frame)."""
+        frame). ``max_anisotropy``: when not None, every layer goes through :meth:`resolve_aniso` with that tap limit,
+        under the bias ``mip_lod_bias`` (0 when that is None) and the same rule for the band."""
         v = view.to_c()
         rows = max(v.row_end - v.row_begin, 0)
         dev = torch.device("cuda", self.device)
@@ -666,7 +680,10 @@ class ShadingContext:
                                  stream=stream)
             if self.raster_layer_stats(stream)["layer_fragments"] == 0:
                 return k, True
-            if mip_lod_bias is None:
+            if max_anisotropy is not None:
+                self.resolve_aniso(attrs, max_anisotropy, 0.0 if mip_lod_bias is None else mip_lod_bias,
+                                   out=(gb, coverage), stream=stream)
+            elif mip_lod_bias is None:
                 self.resolve(attrs, filter, out=(gb, coverage), stream=stream)
             else:
                 self.resolve_mip(attrs, mip_lod_bias, out=(gb, coverage), stream=stream)

@@ -1,10 +1,11 @@
-"""Render one minified view twice on the GPU -- a textured floor that recedes to the horizon under one of the committed
-1K tile sets, rasterised, resolved and shaded on the device -- once with the level-0 linear filter
-(pbr_resolve_materials) and once with the mip-mapped trilinear filter (pbr_generate_mips + pbr_resolve_materials_mip,
-DESIGN.md §11), and write both as PNG.
+"""Render one minified view three times on the GPU -- a textured floor that recedes to the horizon under one of the
+committed 1K tile sets, rasterised, resolved and shaded on the device -- with the level-0 linear filter
+(pbr_resolve_materials), with the mip-mapped trilinear filter (pbr_generate_mips + pbr_resolve_materials_mip) and with
+the anisotropic filter (pbr_resolve_materials_aniso), and write each as PNG. Per image: the grain of the
+far floor; then per filter the error of its albedo plane against a supersampled ground truth.
 
-    python tools/render_mip_floor.py [--width 960 --height 540] [--tile 0] [--lod-bias 0]
-                                     [--out-dir build/mip_floor]
+    python tools/render_mip_floor.py [--width 960 --height 540] [--tile 0] [--lod-bias 0] [--max-anisotropy 8]
+                                     [--truth-scale 8] [--out-dir build/mip_floor]
 """
 import argparse
 import os
@@ -33,12 +34,34 @@ def floor_mesh(half_width, depth, tiles_per_unit):
     return Mesh(v, np.array([0, 3, 2, 0, 2, 1], np.uint32))
 
 
+def floor_grid_mesh(half_width, depth, tiles_per_unit, nx, nz):
+    """floor_mesh as a grid of nx x nz cells: at the supersampled resolution the one quad's near corners fall outside
+    the rasteriser's guard band (32768 pixels) and its triangles would be skipped; the grid's cells that reach so far
+    are off screen."""
+    xs, zs = np.linspace(-half_width, half_width, nx + 1), np.linspace(0.0, depth, nz + 1)
+    gz, gx = np.meshgrid(zs, xs, indexing="ij")
+    v = np.zeros(((nz + 1) * (nx + 1), 14), np.float32)
+    v[:, 0], v[:, 2] = gx.ravel(), gz.ravel()
+    v[:, 3:6] = (0, 1, 0)
+    v[:, 6:9] = (1, 0, 0)
+    v[:, 9:12] = (0, 0, -1)
+    v[:, 12] = (v[:, 0] + half_width) * tiles_per_unit
+    v[:, 13] = (depth - v[:, 2]) * tiles_per_unit
+    j, i = np.meshgrid(np.arange(nz), np.arange(nx), indexing="ij")
+    p00 = (j * (nx + 1) + i).ravel()
+    p10, p01, p11 = p00 + 1, p00 + nx + 1, p00 + nx + 2
+    idx = np.stack([p00, p01, p11, p00, p11, p10], 1).astype(np.uint32)  # floor_mesh's winding: (0, 3, 2), (0, 2, 1)
+    return Mesh(v, idx.ravel())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--width", type=int, default=960)
     ap.add_argument("--height", type=int, default=540)
     ap.add_argument("--tile", type=int, default=0, help="which of the committed 1K tile sets covers the floor")
     ap.add_argument("--lod-bias", type=float, default=0.0)
+    ap.add_argument("--max-anisotropy", type=int, default=8)
+    ap.add_argument("--truth-scale", type=int, default=8, help="supersampling per axis of the albedo ground truth")
     ap.add_argument("--out-dir", default=os.path.join(ROOT, "build", "mip_floor"))
     a = ap.parse_args()
     cfg = S.CONFIGS[4]
@@ -51,15 +74,18 @@ def main():
                        flags=N.PBR_FLAG_F0_PLANE)
     os.makedirs(a.out_dir, exist_ok=True)
     with ShadingContext(0) as ctx:
-        ctx.set_meshes([floor_mesh(40.0, 300.0, 0.5)])
+        ctx.set_meshes([floor_mesh(40.0, 300.0, 0.5), floor_grid_mesh(40.0, 300.0, 0.5, 160, 300)])
         ctx.set_materials(mats, texs)
         ctx.generate_mips()
         ctx.set_pass(pc)
         ctx.set_sky_map(envmap.procedural_sky_rgba16(512, 256))
         at = ctx.rasterize([Draw(mesh=0, material=a.tile, cull=1)], view)
+        albedo = {}
         for name, resolve in (("linear", lambda: ctx.resolve(at, N.PBR_FILTER_LINEAR)),
-                              ("trilinear", lambda: ctx.resolve_mip(at, a.lod_bias))):
+                              ("trilinear", lambda: ctx.resolve_mip(at, a.lod_bias)),
+                              ("aniso8", lambda: ctx.resolve_aniso(at, a.max_anisotropy, a.lod_bias))):
             gb, cov = resolve()
+            albedo[name] = gb.planes[6:9, :, :a.width].clone()
             img = ctx.shade_frame(gb, coverage=cov, fmt=N.PBR_OUTPUT_RGBA8_UNORM)
             torch.cuda.synchronize()
             out = os.path.join(a.out_dir, f"mip_floor_{name}.png")
@@ -68,6 +94,18 @@ def main():
             far = img[: a.height // 2 + a.height // 8].float()
             print(f"{name}: {a.width}x{a.height} floor covered {float((cov != 0).float().mean()):.3f}, mean |dx| of the "
                   f"upper rows' RGB {float((far[:, 1:, :3] - far[:, :-1, :3]).abs().mean()):.2f} / 255 -> {os.path.basename(out)}")
+        # the ground truth of the albedo plane: the same view rasterised at s x s the resolution, resolved with the
+        # level-0 linear filter and box-averaged down; the mean absolute error of each filter's albedo against it
+        s = a.truth_scale
+        big = S.look_at_view((0.0, 1.2, -1.0), (0.0, 0.9, 6.0), float(np.pi / 3), a.width * s, a.height * s, far=400.0)
+        gb, tcov = ctx.resolve(ctx.rasterize([Draw(mesh=1, material=a.tile, cull=1)], big), N.PBR_FILTER_LINEAR)
+        truth = gb.planes[6:9, :, :a.width * s].reshape(3, a.height, s, a.width, s).mean(dim=(2, 4))
+        torch.cuda.synchronize()
+        print(f"truth: {a.width * s}x{a.height * s} floor covered {float((tcov != 0).float().mean()):.3f}")
+        for name, plane in albedo.items():
+            err = (plane - truth).abs()
+            print(f"{name}: albedo mean |error| against the {s}x{s} supersampled level-0 resolve {float(err.mean()):.5f}, "
+                  f"upper rows {float(err[:, : a.height // 2 + a.height // 8].mean()):.5f}")
 
 
 if __name__ == "__main__":

@@ -10,7 +10,12 @@ to the same device G-buffer and against the box's streaming rate, in one process
   (d) the trilinear resolve (pbr_resolve_materials_mip) beside (a)'s linear leg, the yardstick of this leg: (i) lod 0
       everywhere (a bias of -64 clamps every sample to level 0: the magnified case, one bilinear per sample), the
       scene's own footprints (bias 0), (ii) bias 1.5 (every sample between two levels: two bilinears); and
-      pbr_generate_mips on the scene's textures (host clock: the call synchronises its stream).
+      pbr_generate_mips on the scene's textures (host clock: the call synchronises its stream);
+  (e) the anisotropic resolve (pbr_resolve_materials_aniso), each leg beside the leg of (d) that samples as many
+      levels, with that leg's own min / max over its median as the spread: max_anisotropy 1 (the trilinear fetches through
+      the tap loop) under bias 0 and 1.5, max_anisotropy 8 on the scene's own footprints, and a worst case --
+      the scene's attributes under a 10 : 1 UV ramp and bias 0.5, every sample 8 taps on two levels -- with its time
+      per bilinear against (ii)'s.
 
     python tools/resolve_bench.py [--width 3840 --height 2160] [--steps 50] [--log profiles/r09/resolve_bench.log]
 
@@ -130,6 +135,44 @@ def main():
             r = event_ms(lambda: ctx.resolve_mip(attrs, bias, out=out), a.steps)
             r.update(leg="d_resolve_mip_" + name, lod_bias=bias, gb_per_s=total / (r["median_ms"] * 1e-3) / 1e9,
                      over_linear=r["median_ms"] / res["linear"]["median_ms"])
+            res["mip_" + name] = r
+            emit(r)
+        # (e) the anisotropic resolve beside (d)'s legs of the same run, the yardsticks of these legs
+        for bias in (0.0, 1.5):
+            same = torch.equal(ctx.resolve_aniso(attrs, 1, bias)[0].planes.view(torch.int32),
+                               ctx.resolve_mip(attrs, bias)[0].planes.view(torch.int32))
+            emit({"check": "anisotropic with max_anisotropy 1 == trilinear planes", "lod_bias": bias,
+                  "bit_identical": bool(same)})
+            if not same:
+                sys.exit("resolve_bench: the anisotropic resolve with one tap differs from the trilinear resolve")
+        # the worst case: the scene's attributes under a UV ramp of 10 : 1 texels per pixel (x : y; every texture of the
+        # scene has one size), so every sample whose quad partners are valid takes max_anisotropy = 8 taps, at
+        # r2 = 100 / 64 plus a bias of 0.5: between levels 0 and 1, two levels of 8 bilinears each
+        size = float(texs[0].shape[1])
+        assert all(t.shape[0] == size and t.shape[1] == size for t in texs)
+        worst_planes = attrs.planes.clone()
+        worst_planes[12] = torch.arange(worst_planes.shape[2], device=dev, dtype=torch.float32)[None, :] * (10.0 / size)
+        worst_planes[13] = torch.arange(worst_planes.shape[1], device=dev, dtype=torch.float32)[:, None] * (1.0 / size)
+        worst = type(attrs)(worst_planes, attrs.material, attrs.width)
+        ids = attrs.material[:attrs.height // 2 * 2, :attrs.width // 2 * 2]  # whole quads
+        geometry = (ids.int() & 0xFFFF) < len(mats)
+        pairs_x = (ids[:, 0::2] == ids[:, 1::2]).repeat_interleave(2, dim=1)
+        pairs_y = (ids[0::2] == ids[1::2]).repeat_interleave(2, dim=0)
+        full = float((geometry & pairs_x & pairs_y).sum()) / float(geometry.sum())
+        for name, m, bias, at, yard, taps in (("m1_bias0", 1, 0.0, attrs, "mip_bias0", None),
+                                             ("m1_bias1.5", 1, 1.5, attrs, "mip_bias1.5", None),
+                                             ("m8_bias0", 8, 0.0, attrs, "mip_bias0", None),
+                                             ("m8_worst", 8, 0.5, worst, "mip_bias1.5", 16)):
+            out = ctx.resolve_aniso(at, m, bias)
+            r = event_ms(lambda: ctx.resolve_aniso(at, m, bias, out=out), a.steps)
+            y = res[yard]
+            r.update(leg="e_resolve_aniso_" + name, max_anisotropy=m, lod_bias=bias,
+                     gb_per_s=total / (r["median_ms"] * 1e-3) / 1e9, yardstick="d_resolve_" + yard,
+                     over_yardstick=r["median_ms"] / y["median_ms"],
+                     yardstick_spread=[y["min_ms"] / y["median_ms"], y["max_ms"] / y["median_ms"]])
+            if taps:  # bilinears per sample here against the yardstick's two
+                r.update(bilinears_per_sample=taps, samples_with_every_tap=full,
+                         ms_per_bilinear_over_yardstick=(r["median_ms"] / taps) / (y["median_ms"] / 2.0))
             emit(r)
         # (c) device-to-device copy moving the same bytes (half read, half written)
         src = torch.empty(total // 2, dtype=torch.uint8, device=dev)
