@@ -105,9 +105,32 @@ def checker_ids(h, w, n_materials):
     return ((xs + ys * 4) % n_materials).astype(np.uint16)
 
 
-def device_resolve(ctx, attrs, ids, filt, stride=None, device=None, stream=None, rows=None):
+def padded_inputs(attrs, ids, stride, pad=False):
+    """(attrs (14, h, stride) float32, ids (h, stride) uint16) as the device helpers upload them. Default: the padding
+    columns hold NaN and id 0xFFFF. ``pad``: they hold a believable geometry pixel instead -- the id of the row's last
+    column, its attributes where they are finite (0.5 where not), and UVs that continue the row's ramp (the last
+    column plus one, two ... times the step between the last two columns; 1 / 8 where the row has one column or the
+    step is not finite) -- so a kernel that took a padding column for a partner would see a valid one."""
+    _, h, w = attrs.shape
+    a = np.full((14, h, stride), np.nan, np.float32)
+    i = np.full((h, stride), 0xFFFF, np.uint16)
+    a[:, :, :w], i[:, :w] = attrs, ids
+    if pad and stride > w:
+        with np.errstate(all="ignore"):
+            last = np.where(np.isfinite(attrs[:, :, w - 1]), attrs[:, :, w - 1], np.float32(0.5))
+            step = attrs[12:14, :, w - 1] - attrs[12:14, :, w - 2] if w >= 2 else np.full((2, h), np.nan, np.float32)
+            step = np.where(np.isfinite(step), step, np.float32(0.125)).astype(np.float32)
+            for j in range(stride - w):
+                a[:, :, w + j] = last
+                a[12:14, :, w + j] = last[12:14] + np.float32(j + 1) * step
+                i[:, w + j] = ids[:, w - 1]
+    return a, i
+
+
+def device_resolve(ctx, attrs, ids, filt, stride=None, device=None, stream=None, rows=None, pad=False):
     """Upload (with `stride` elements per row), resolve into sentinel-filled canvases of the same stride, return
-    (planes (15, h, stride), opacity (h, stride), coverage (h, stride)) as numpy, synchronised."""
+    (planes (15, h, stride), opacity (h, stride), coverage (h, stride)) as numpy, synchronised. ``pad``: the input
+    padding columns hold a valid-looking pixel (padded_inputs) instead of NaN and id 0xFFFF."""
     import torch
 
     from physically_based_renderer_amd.renderer import Attributes, GBuffer
@@ -115,10 +138,9 @@ def device_resolve(ctx, attrs, ids, filt, stride=None, device=None, stream=None,
     device = torch.device("cuda", 0) if device is None else device
     _, h, w = attrs.shape
     stride = w if stride is None else stride
-    ta = torch.full((14, h, stride), float("nan"), dtype=torch.float32, device=device)
-    ta[:, :, :w] = torch.from_numpy(attrs).to(device)
-    ti = torch.full((h, stride), -1, dtype=torch.int16, device=device)
-    ti[:, :w] = torch.from_numpy(ids.view(np.int16)).to(device)
+    pa, pi = padded_inputs(attrs, ids, stride, pad)
+    ta = torch.from_numpy(pa).to(device)
+    ti = torch.from_numpy(pi.view(np.int16)).to(device)
     at = Attributes(ta, ti, width=w)
     planes = torch.full((15, h, stride), float(SENTINEL), dtype=torch.float32, device=device)
     opacity = torch.full((h, stride), float(SENTINEL), dtype=torch.float32, device=device)

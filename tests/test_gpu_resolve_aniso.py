@@ -312,7 +312,8 @@ def test_bounds_checked_build_is_clean_and_equal(tmp_path, gpu):
     mats, texs, cases = AC.bounds_cases()
     for name, attrs, ids, m, bias, stride in cases:
         got = (z[name + "__planes"], z[name + "__opacity"], z[name + "__coverage"])
-        check(got, RA.resolve_aniso(attrs, ids, mats, texs, m, bias), 70, "debug-bounds " + name)
+        assert attrs.shape[2] == (71 if name.startswith("odd") else 70) and got[0].shape[2] == stride
+        check(got, RA.resolve_aniso(attrs, ids, mats, texs, m, bias), attrs.shape[2], "debug-bounds " + name)
 
 
 # ---- end to end ---------------------------------------------------------------------------------------------------------

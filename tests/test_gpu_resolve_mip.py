@@ -295,7 +295,8 @@ def test_tables_swapped_between_queued_calls_on_two_streams(gpu, table, chains):
 
 
 def test_bounds_checked_build_is_clean_and_equal(tmp_path, gpu):
-    """resolve_mip_cases.bounds_case() under _lib/debug_bounds/libpbrshade.so in a fresh child process (PBR_LIB_PATH):
+    """resolve_mip_cases.BOUNDS_RUNS (bounds_case() at 70 columns, bounds_case_odd_width() at 71) under
+    _lib/debug_bounds/libpbrshade.so in a fresh child process (PBR_LIB_PATH):
     generation and resolve flag no index class -- slots, level table, both texel buffers are class "texel" -- and the
     result equals the restatement."""
     if not os.path.exists(C.DEBUG_LIB):
@@ -308,9 +309,13 @@ def test_bounds_checked_build_is_clean_and_equal(tmp_path, gpu):
     assert str(z["flavor"]) == "debug_bounds" and str(z["sources_sha"]) == N.kernel_sources_sha()  # of this checkout
     assert (z["bounds"] < 0).all(), f"bounds violations (gbuffer/output/coverage/texel/light/lds): {z['bounds']}"
     mats, texs, attrs, ids = MC.bounds_case()
-    for name, bias in (("bias0_71", 0.0), ("bias1.5_70", 1.5)):
+    odd = MC.bounds_case_odd_width()
+    assert [r[0] for r in MC.BOUNDS_RUNS[:2]] == ["bias0_71", "bias1.5_70"]
+    for name, odd_width, bias, stride in MC.BOUNDS_RUNS:
+        a, i = odd if odd_width else (attrs, ids)
         got = (z[name + "__planes"], z[name + "__opacity"], z[name + "__coverage"])
-        check(got, RM.resolve_mip(attrs, ids, mats, texs, bias), 70, "debug-bounds " + name)
+        assert got[0].shape[2] == stride
+        check(got, RM.resolve_mip(a, i, mats, texs, bias), a.shape[2], "debug-bounds " + name)
 
 
 # ---- end to end ---------------------------------------------------------------------------------------------------------
