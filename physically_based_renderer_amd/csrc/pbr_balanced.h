@@ -10,7 +10,9 @@
 //   1. (pass 1) tests every (pixel, light) pair with a cheap conservative back-face test (below) and keeps a
 //      64-bit mask of the lights that may reach each of its 128 pixels;
 //   2. ranks its pixels by live-light count (LDS counting sort) and re-pairs them across lanes, the k-th
-//      smallest count with the k-th largest, moving each pixel's loop invariants through LDS;
+//      smallest count with the k-th largest, moving each pixel's loop invariants through LDS -- over the
+//      workgroup's 512 pixels where all four waves take this path (BalancedWaveLds::vote: thread t then evaluates
+//      ranks t and 511 - t), else over the wave's own 128;
 //   3. (pass 2) lets every lane walk its two pixels' live lights one after the other, TWO lights of the
 //      current pixel per iteration in packed fp32 (the pixel's invariants are splat operands, the two lights'
 //      records per element) -- the cycles of one packed pair-loop iteration for two items, ~L/4 iterations
@@ -114,11 +116,23 @@ constexpr int kBalRecX = 6;        // float4 per exchanged pixel record, exact p
 
 struct BalancedWaveLds {
     float4 rec[64 * kBalRec];  // 7 KiB: the exchanged records; then each evaluating lane's two results (float4 0, 1)
-    union {
-        int hist[64];          // ranking
-        int2 rank[64];         // by owner lane: the ranks of its two pixels (pass 2 -> hand-back)
+    int hist[64];              // ranking: the wave's pixels per live count (block ranking: read by all four waves)
+    union {                    // touched by the wave itself only
+        int base[64];          // ranking: the first rank of the wave's pixels of each count
+        int2 back[64];         // by owner lane: the LDS addresses of its two pixels' results (pass 2 -> hand-back)
     };
+    // The wave's vote for ranking with the whole workgroup (1: it runs the balanced pass of this launch and per-wave
+    // ranking is not forced), written before the vote's block barrier, which every wave of a balanced kernel executes
+    // once: the workgroup ranks together where all four are set (block_vote). Kept here, not in registers, through
+    // pass 2.
+    int vote, pad_[3];
 };
+
+// Block-uniform: all four waves of the workgroup voted to rank together (`w`: this wave's region, number `wv`).
+__device__ __forceinline__ bool block_vote(const BalancedWaveLds& w, int wv) {
+    const BalancedWaveLds* b = &w - wv;
+    return __builtin_amdgcn_readfirstlane(b[0].vote & b[1].vote & b[2].vote & b[3].vote) != 0;
+}
 
 // The per-pixel loop invariants of the faithful scaled lean loop (the scalar view of PixelInvariants2 after
 // faithful_scale plus Faithful2), the pixel's live-light mask and where it came from.
@@ -207,9 +221,9 @@ __device__ __forceinline__ ItemPixel load_item(const float4* src) {
 
 // The exact (default-mode) record: the lean-loop invariants of make_invariants in brdf_x2's QUARTER form (N / 4, k / 4,
 // 16 N.V: exact scalings), less the three that are one subtraction from another field (1 - F0, a^2 - 1, 1 - k:
-// re-derived by load_item_x with the same operation on the unscaled value, so bit for bit the same values). The pixel's sum so far (its directional lights), from which the
-// evaluating lane continues in the reference's order, travels separately (BalancedWaveLds::start): written by
-// the owner before the exchange, it is not held in registers through it.
+// re-derived by load_item_x with the same operation on the unscaled value, so bit for bit the same values). No sum
+// travels with it: exact balanced passes have no directional lights (PassArgs::balanced == 2), so every pixel's sum
+// starts at +0 in the evaluating lane and runs through its live lights in the reference's order.
 struct ItemPixelX {
     f3 pos, n, v, albedo, f0, omf0;
     float omm, a_sqr, a2m1, k, omk, ggx_v, nv4;
@@ -288,6 +302,18 @@ __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+// LDS traffic between the lanes of the ranking group: the workgroup (`block`, block-uniform: every wave of the
+// workgroup executes this call) or the wave. The explicit wait covers the records written by inline asm
+// (lds_write2), which the compiler's own wait counting does not see: they must have landed before the barrier
+// lets another wave read them.
+__device__ __forceinline__ void group_lds_sync(bool block) {
+    if (block) {
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __syncthreads();
+    } else {
+        wave_lds_sync();
+    }
 }
 
 // Pass 1 runs in fast-window waves only (lean and faithful or exact lean: every position |x| <= 2^20, every light inside
@@ -413,7 +439,11 @@ __device__ __forceinline__ void faithful_point_items2(const ItemPixel& q, const 
     const v2 x2 = x * x;
     const v2 x4 = x2 * x2;
     v2 p = x4 * x;  // pow5_fast3's products
-    if (__builtin_expect(((lanes(svl.x < kBalNearVL) | lanes(svl.y < kBalNearVL)) & live) != 0, 0)) {
+    // `!(>=)`, not `<`: with V + L exactly 0 sqrt_nr's seed is 0 * inf and svl is NaN, which must take this branch too
+    // (as `<` it did only when another lane of the wave happened to take it in the same iteration, so whether such a
+    // pixel was redone depended on which lanes shared its wave). The two compares differ only for NaN: the build's
+    // -fno-fast-math (csrc/Makefile FPFLAGS) is what keeps the compiler from folding `!(x >= c)` into `x < c`.
+    if (__builtin_expect(((lanes(!(svl.x >= kBalNearVL)) | lanes(!(svl.y >= kBalNearVL))) & live) != 0, 0)) {
         ok &= ge(svl, 0x1p-30f);  // normalize_x2's window
         if (x.x > PBR_POW5_FAST3_GLIBC_FROM && on(live)) p.x = pow5_glibc(x.x);  // pow5_fast3's band
         if (x.y > PBR_POW5_FAST3_GLIBC_FROM && on(live)) p.y = pow5_glibc(x.y);
@@ -624,7 +654,11 @@ __device__ __forceinline__ int wave_live_items(const BalMasks& bm) {
 // The whole balanced pass over the point lights of an untiled lean wave (at most kBalMaxLights). `live_a` /
 // `live_b` say which of the pair's pixels take part (geometry); `lds_lights`: the pass's point lights staged by
 // the block (stage_balanced_lights); `bm`: their live masks from balanced_pass1. ORs the pixels that left the
-// fast-path window for a live item into `redo`. Wave-uniform control flow; no block barrier.
+// fast-path window for a live item into `redo`. Wave-uniform control flow. `w` is the wave's own region of the
+// workgroup's array (region i belongs to wave i). Where all four waves voted for it (BalancedWaveLds::vote, set by the
+// kernel: then every wave of the workgroup is in this call) they rank together, which takes five block barriers
+// (3-7 below) after the vote's own (2), the only one executed otherwise. The numbers are those of DESIGN.md 5h's list,
+// which counts the kernel's staging barrier as 1.
 // EXACT (the default mode's lean loop, bit-identical to the uniform loop): q is unscaled, `sum` holds the pair's
 // directional-light sums on entry; each pixel's sum continues from it through its live lights in increasing
 // light order (element 0 of an iteration is the smaller light; the skipped terms are the +-0 the reference adds),
@@ -641,24 +675,47 @@ __device__ __forceinline__ void lighting_balanced_points(const PixelInvariants2&
     BAL_PROF_T(t1);
     PBR_PHASE("rank");
 
-    // ---- rank the wave's 128 pixels by live count (counting sort; ties in LDS-atomic order, which only
-    // decides which lane evaluates a pixel, never how)
+    // ---- rank the group's pixels by live count (counting sort; ties in wave, then LDS-atomic order, which only
+    // decides which lane evaluates a pixel, never how). The group: the wave's 128 pixels, or after a unanimous vote the
+    // workgroup's 512 -- the same steps with three parameters: the number of ranks, where slot s lives (thread s's
+    // record slot: the four waves' regions are one array, region i = wave i) and the sync between the steps.
+    const int wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x) >> 6;
+    __syncthreads();  // block barrier 2, in either form: the vote's (the other waves take it wherever they voted)
+    const bool block = block_vote(w, wv);
+    BalancedWaveLds* const g0 = block ? &w - wv : &w;  // the group's first region
+    const int top = block ? 511 : 127, half = block ? 256 : 64;
+    auto slot_rec = [&](int s) {  // slot s < half
+        s = PBR_BOUNDS(s, half, kBoundsLds);
+        return &g0[s >> 6].rec[R * (s & 63)];
+    };
     const int cnt_a = __popc(a0) + __popc(a1), cnt_b = __popc(c0) + __popc(c1);
     w.hist[lane_id] = 0;
     wave_lds_sync();
     const int bin_a = cnt_a < 63 ? cnt_a : 63, bin_b = cnt_b < 63 ? cnt_b : 63;
-    const int pos_a = atomicAdd(&w.hist[bin_a], 1);
+    const int pos_a = atomicAdd(&w.hist[bin_a], 1);  // per-wave histograms in both forms: no more contention
     const int pos_b = atomicAdd(&w.hist[bin_b], 1);
-    wave_lds_sync();
-    const int h = w.hist[lane_id];
+    group_lds_sync(block);  // block barrier 3: the four histograms are complete
+    int h = w.hist[lane_id], below = 0;  // lane b: the group's pixels of bin b, those of lower-numbered waves
+    if (block) {
+        const int h0 = g0[0].hist[lane_id], h1 = g0[1].hist[lane_id], h2 = g0[2].hist[lane_id],
+                  h3 = g0[3].hist[lane_id];
+        below = (wv > 0 ? h0 : 0) + (wv > 1 ? h1 : 0) + (wv > 2 ? h2 : 0);
+        h = (h0 + h1) + (h2 + h3);
+    }
     const int incl = wave_scan_add_dpp(h);
+    // The first rank of this wave's pixels of each bin: the group's exclusive prefix plus the lower waves' share. In
+    // an array of the wave's own, so that no barrier has to separate the other waves' histogram reads from it.
+    w.base[lane_id] = (incl - h) + below;
     wave_lds_sync();
-    w.hist[lane_id] = incl - h;  // exclusive prefix: first rank of each bin
+    const int rank_a = w.base[bin_a] + pos_a, rank_b = w.base[bin_b] + pos_b;
     wave_lds_sync();
-    const int rank_a = w.hist[bin_a] + pos_a, rank_b = w.hist[bin_b] + pos_b;
-    wave_lds_sync();
-    w.rank[lane_id] = make_int2(rank_a, rank_b);  // read back at the hand-back (nothing of it lives through pass 2)
-    // rank r < 64 -> lane r, first pixel; r >= 64 -> lane 127 - r, second pixel.
+    // rank r < half -> slot r, first pixel; r >= half -> slot top - r, second pixel. Where the evaluating lane will
+    // leave each result (float4 0 or 1 of that slot) is kept for the hand-back, in LDS: nothing of the ranking lives
+    // in registers through pass 2.
+    const int ra_ = PBR_BOUNDS(rank_a, top + 1, kBoundsLds), rb_ = PBR_BOUNDS(rank_b, top + 1, kBoundsLds);
+    float4* const rec_a = slot_rec(ra_ < half ? ra_ : top - ra_);
+    float4* const rec_b = slot_rec(rb_ < half ? rb_ : top - rb_);
+    w.back[lane_id] = make_int2((int)lds_addr(rec_a) + (ra_ < half ? 0 : 16), (int)lds_addr(rec_b) + (rb_ < half ? 0 : 16));
     using Item = std::conditional_t<EXACT, ItemPixelX, ItemPixel>;
     Item ia, ib;
     if constexpr (EXACT) {
@@ -669,15 +726,15 @@ __device__ __forceinline__ void lighting_balanced_points(const PixelInvariants2&
         ib = item_pixel(q, fi, pos, 1, c0, c1, 2 * lane_id + 1);
     }
     // Phase 0: the small-count pixels.
-    if (rank_a < 64) store_item(&w.rec[R * rank_a], ia);
-    if (rank_b < 64) store_item(&w.rec[R * rank_b], ib);
-    wave_lds_sync();
+    if (rank_a < half) store_item(rec_a, ia);
+    if (rank_b < half) store_item(rec_b, ib);
+    group_lds_sync(block);  // block barrier 4: every slot holds its first record
     Item cur = load_item_any<EXACT>(&w.rec[R * lane_id]);
-    wave_lds_sync();
+    group_lds_sync(block);  // block barrier 5: ... and has been read, so the second records may replace them
     // Phase 1: the large-count pixels stay in LDS; a lane reads its second pixel when it switches.
-    if (rank_a >= 64) store_item(&w.rec[R * (127 - rank_a)], ia);
-    if (rank_b >= 64) store_item(&w.rec[R * (127 - rank_b)], ib);
-    wave_lds_sync();
+    if (rank_a >= half) store_item(rec_a, ia);
+    if (rank_b >= half) store_item(rec_b, ib);
+    group_lds_sync(block);  // block barrier 6: every slot holds its second record
 
     BAL_PROF_T(t2);
     PBR_PHASE("pass2");
@@ -783,15 +840,18 @@ __device__ __forceinline__ void lighting_balanced_points(const PixelInvariants2&
     }
     BAL_PROF_T(t3);
     PBR_PHASE("handback");
-    // ---- hand the results back: the owner reads its two pixels' from their evaluating lanes' slots (rank r < 64:
-    // lane r, first pixel; r >= 64: lane 127 - r, second pixel)
-    wave_lds_sync();
-    const int2 rk = w.rank[lane_id];
-    auto slot = [&](int r) {
-        r = PBR_BOUNDS(r, 128, kBoundsLds);
-        return r < 64 ? R * r : R * (127 - r) + 1;
-    };
-    const float4 ra = w.rec[slot(rk.x)], rb = w.rec[slot(rk.y)];
+    // ---- hand the results back: the owner reads its two pixels' from their evaluating lanes' slots (the addresses
+    // kept at the ranking; the vote is read again rather than carried through the loop)
+    group_lds_sync(block_vote(w, wv));  // block barrier 7: every wave's results are in their slots
+    // The ranks and slots behind these addresses went through PBR_BOUNDS where they were formed. The casts go from the
+    // LDS address space, so the loads are ds_read_b128 (as four typed float loads the constant-ambient faithful
+    // kernel spilled 20 B per lane).
+    typedef __attribute__((address_space(3))) const char lds_char;
+    const int2 bk = w.back[lane_id];
+    const float4 ra = *(const float4*)(lds_char*)(uintptr_t)(uint32_t)bk.x,
+                 rb = *(const float4*)(lds_char*)(uintptr_t)(uint32_t)bk.y;
+    // Nothing writes a record slot after this in the launch (the finish and the exact re-pass use none of this LDS), so
+    // the waves need not meet again.
     wave_lds_sync();
     if constexpr (EXACT)
         sum = f3x2{v2{ra.x, rb.x}, v2{ra.y, rb.y}, v2{ra.z, rb.z}};

@@ -310,6 +310,7 @@ int pbr_context_create(int device, pbr_context** out_ctx) {
     if (const char* e = std::getenv("PBR_PIXELS_PER_THREAD")) ctx->pixels_per_thread = std::atoi(e) == 1 ? 1 : 2;
     if (const char* e = std::getenv("PBR_BALANCED_MIN")) ctx->balanced_min = std::atoi(e);
     if (const char* e = std::getenv("PBR_LEAN")) ctx->lean = std::atoi(e) != 0;
+    if (const char* e = std::getenv("PBR_RANK_PER_WAVE")) ctx->rank_per_wave = std::atoi(e) != 0;
     DeviceGuard g(device);
     if (!g.ok) {
         delete ctx;
@@ -589,6 +590,7 @@ int shade(pbr_context* ctx, const pbr_gbuffer_soa* gb, const pbr_frame_desc* fr,
                     : a.ps.faithful == 1                                   ? 1
                     : a.ps.faithful == 0 && !a.exact_only && a.ps.n_dir == 0 && ctx->points_quarter_ok ? 2
                                                                            : 0;
+    if (a.ps.balanced != 0 && ctx->rank_per_wave) a.ps.balanced |= pbr::kBalRankPerWave;
 
     if (const int rc = en.open(stream, "shade stream")) return rc;
     const hipStream_t s = en.s;

@@ -155,6 +155,7 @@ struct pbr_context {
     // and no spot lights; -1: the measured crossover of the mode (kBalancedMinFaithful / kBalancedMinExact);
     // PBR_BALANCED_MIN overrides both (0 disables).
     int balanced_min = -1;
+    bool rank_per_wave = false;  // PBR_RANK_PER_WAVE: the balanced kernels rank per wave in every workgroup (development)
     bool points_flag_ok = false;  // pbr_set_pass: every point light inside the fast-path window
     bool points_quarter_ok = false;  // ... and every point strength inside the quarter gate (the exact balanced items' 4x radiance)
     int pixels_per_thread = 2;  // kernel layout: packed pixel pairs (measured faster); PBR_PIXELS_PER_THREAD=1 overrides

@@ -28,7 +28,7 @@ enum BoundsClass {
     kBoundsCoverage = 2,  // coverage byte read
     kBoundsTexel = 3,     // sky / environment texel (y * w + x < w * h)
     kBoundsLight = 4,     // light record (j < n_dir + n_point + n_spot)
-    kBoundsLds = 5,       // balanced lists: light index <= kBalMaxLights (the zero sentinel), list slot < 128
+    kBoundsLds = 5,       // balanced lists: light index <= kBalMaxLights (the zero sentinel), rank < 128 or 512, record slot < half
     kBoundsRaster = 6,    // rasteriser scratch (raster.h): draw table, vertex records, large list, visibility words
     kBoundsMesh = 7,      // rasteriser mesh data: vertex and index buffers
     kBoundsClasses = 8

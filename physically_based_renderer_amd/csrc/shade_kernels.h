@@ -34,10 +34,16 @@ struct PassArgs {
     int sky_w, sky_h;
     int eye_ok;  // the eye position is inside the fast-path window (0 or |x| in [2^-20, 2^20]), host-checked
     int balanced;  // untiled pass whose point lights take the wave-balanced lists (pbr_balanced.h): 0 no,
-                   // 1 faithful pass (no spot lights), 2 exact pass (no spot or directional lights)
+                   // 1 faithful pass (no spot lights), 2 exact pass (no spot or directional lights); with 1 or 2,
+                   // | kBalRankPerWave (development, PBR_RANK_PER_WAVE): rank each wave's 128 pixels on its own in
+                   // every workgroup, never the workgroup's 512 together. A bit here, not a field: four more bytes of
+                   // kernel arguments cost every kernel ~0.3 us per launch (configs 1 and 2)
     int faithful;  // PBR_FLAG_FAITHFUL: 0 off; 1 on (host preconditions hold); 2 on, culled pass with > 64
                    // lights: the kernel counts each wave's summed terms against the bound's 64
 };
+
+constexpr int kBalKindMask = 3;      // PassArgs::balanced: the variant (0, 1, 2)
+constexpr int kBalRankPerWave = 4;   // ... and the per-wave ranking switch
 
 constexpr int kOutRgba32f = 0;
 constexpr int kOutRgba8 = 1;

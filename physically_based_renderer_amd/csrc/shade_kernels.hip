@@ -137,7 +137,7 @@ std::string launched_kernel(const LaunchArgs& a) {
     const std::string t = std::to_string(a.ambient_mode == kAmbientIblDiffuse ? 1 : 0) + ", " + b(a.f0_plane) + ", " +
                           b(a.apply_ao) + ", " + b(a.cull);
     if (a.pixels_per_thread != 2) return "shade_tile1_kernel<" + t + ">";
-    if (!a.cull && a.ps.balanced != 0) return "shade_tile_kernel<" + t + ", " + std::to_string(a.ps.balanced) + ">";
+    if (!a.cull && a.ps.balanced != 0) return "shade_tile_kernel<" + t + ", " + std::to_string(a.ps.balanced & kBalKindMask) + ">";
     if (a.lean) return "shade_lean_kernel<" + t + ", " + b(a.ps.faithful != 0) + ">";
     return "shade_tile_kernel<" + t + ", 0>";
 }

@@ -14,7 +14,7 @@ namespace pbr {
 
 template <int AMBIENT, bool F0_PLANE, bool APPLY_AO>
 hipError_t launch_balanced(const LaunchArgs& a, dim3 grid, hipStream_t stream) {
-    if (a.ps.balanced == 1)
+    if ((a.ps.balanced & kBalKindMask) == 1)
         hipLaunchKernelGGL((shade_tile_kernel<AMBIENT, F0_PLANE, APPLY_AO, false, 1>), grid, dim3(kBlock), 0, stream,
                            a.gb, a.ps, a.lights, a.env, a.frame, a.tile_kept, a.exact_only);
     else

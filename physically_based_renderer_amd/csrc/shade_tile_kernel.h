@@ -100,6 +100,22 @@ __global__ __launch_bounds__(kBlock, PBR_X2_MIN_WAVES) void shade_tile_kernel(
     f3x2 d2 = splat3(0.0f, 0.0f, 0.0f);
     bool faithful_wave = false;  // wave-uniform: the faithful loop ran, so the finish may be faithful too
     TL_RT(3);
+    // The balanced variants: one vote of the workgroup, in which every wave takes part whatever path it chooses below.
+    // A wave that runs this instantiation's balanced pass votes for ranking with the whole workgroup and meets the
+    // others at the vote's barrier after its pass 1 (lighting_balanced_points); every other wave -- outside the frame,
+    // background only, on another light loop, an exact_only pass -- votes no and takes the barrier at once. Where all
+    // four vote yes they rank and exchange their 512 pixels together (pbr_balanced.h), and that unanimity is what makes
+    // block barriers legal inside a path the waves otherwise choose one by one; else each balanced wave ranks its own
+    // 128. kBalRankPerWave in ps.balanced (a development switch) makes every vote a no.
+    auto vote = [&](bool yes) {
+        if ((tid & 63) == 0) s.bal[wslot].vote = yes;
+    };
+    auto vote_no = [&]() {
+        if constexpr (BAL != 0) {
+            vote(false);
+            __syncthreads();
+        }
+    };
     if (wave_geometry) {  // wave-uniform
         // Wave-uniform choice of the light loop.
         const v2 nn = dot3(p.n, p.n);
@@ -134,6 +150,7 @@ __global__ __launch_bounds__(kBlock, PBR_X2_MIN_WAVES) void shade_tile_kernel(
                 // unscaled ones once more for the finish. launder() keeps the compiler from merging the
                 // rebuilds with the computation above (which would keep q2 live across the loop: it spilled).
                 PBR_PHASE("pass1");
+                vote(!(ps.balanced & kBalRankPerWave));
                 const BalMasks bm = balanced_pass1<false>(p.pos, p.n, ga, gb_, ps.n_point, kBalDistLoFaithful, s.bal[wslot],
                                                    s.bal_light, prof);
                 bal_items = wave_live_items(bm);
@@ -157,6 +174,7 @@ __global__ __launch_bounds__(kBlock, PBR_X2_MIN_WAVES) void shade_tile_kernel(
                 BAL_PROF_ADD(8, (long long)__builtin_amdgcn_s_memtime() - t_l1);
 #endif
             } else {
+                vote_no();
                 form_q2();
                 if (!CULL) faithful_scale(q2);
 #if PBR_BAL_PROFILE
@@ -174,6 +192,7 @@ __global__ __launch_bounds__(kBlock, PBR_X2_MIN_WAVES) void shade_tile_kernel(
             }
         } else if (faithful_wave) {
             PBR_COLD("faithful_nonlean");
+            vote_no();
             form_q2();
             if (!CULL) faithful_scale(q2);
             d2 = lighting_fast<CULL, false, true>(q2, pos2, fast2, lights, ps, wb, cull_enabled, redo, kept_total);
@@ -201,6 +220,7 @@ __global__ __launch_bounds__(kBlock, PBR_X2_MIN_WAVES) void shade_tile_kernel(
                     p = load_pair<F0_PLANE, APPLY_AO>(gb, ps, va ? rrow : 0, vb ? rrow + 1 : 0,
                                                       vb && gb.pairs_aligned);
                 };
+                vote(!(ps.balanced & kBalRankPerWave));
                 const BalMasks bm = balanced_pass1<true>(p.pos, p.n, ga, gb_, ps.n_point, kBalDistLoExact, s.bal[wslot],
                                                    s.bal_light, prof);
                 bal_items = wave_live_items(bm);
@@ -214,16 +234,19 @@ __global__ __launch_bounds__(kBlock, PBR_X2_MIN_WAVES) void shade_tile_kernel(
                 q2 = pair_invariants(p, ps, fast2);  // the full set: the finish-only one measured slower here (SGPRs)
                 pos2 = p.pos;
             } else {
+                vote_no();
                 form_q2();
                 d2 = lighting_fast<CULL, true>(q2, pos2, fast2, lights, ps, wb, cull_enabled, redo, kept_total);
             }
         } else {
             PBR_COLD("general");
+            vote_no();
             form_q2();
             d2 = lighting_fast<CULL, false>(q2, pos2, fast2, lights, ps, wb, cull_enabled, redo, kept_total);
         }
     } else {
         PBR_COLD("background");
+        vote_no();
         form_q2();  // background only: the sky pass reads N
     }
     TL_RT(4);
