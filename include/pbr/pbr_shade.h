@@ -596,6 +596,81 @@ typedef struct pbr_blend_source {
 int pbr_blend_layer(pbr_context* ctx, const pbr_blend_source* source, const pbr_frame_desc* dst, int32_t width,
                     int32_t height, void* stream);
 
+/* ---- Four samples per pixel: sample coverage, fragments and the multisample resolve (m_4xMsaaState,
+ * SampleDesc.Count = 4: PBRApp.cpp:800-801, d3dApp.cpp:202-203, :382-384, :540-541) -------------------------------
+ * Vertices are snapped to 1/256 pixel and D3D's standard 4-sample positions are multiples of 1/16 pixel, so a sample
+ * lies on the grid and its coverage is as exact as a pixel centre's. Sample s of pixel (x, y)
+ * is at (x + 0.5 + dx_s / 16, y + 0.5 + dy_s / 16) with (dx, dy) = (-2, -6), (6, -2), (-6, 2), (2, 6). Coverage
+ * (top-left rule), the interpolated z and the range test 0 <= z < 1 are pbr_rasterize's, evaluated at the sample; per
+ * sample the nearest fragment wins, an equal z goes to the earlier triangle. The samples of a pixel that the same
+ * triangle won are one *fragment*, as are those that nothing won (the background fragment): a pixel has 1 to 4
+ * fragments, numbered as *slots* in the order of their lowest sample, so slot 0 owns sample 0. Shading is per pixel and
+ * fragment: slot k's attributes are pbr_rasterize's interpolation for that triangle at the pixel CENTRE, inside the
+ * triangle or not (no clamp, no centroid adjustment: D3D's default for inputs without `centroid`, which Default.hlsl
+ * does not use). The caller hands every slot that exists to pbr_resolve_materials and a shading call, unchanged, and
+ * pbr_msaa_resolve averages the four samples of each pixel. The pattern is D3D's standard one; the reference asks for
+ * quality level m_4xMsaaQuality - 1, which is vendor-defined. Additive: PBR_ABI_VERSION stays 9, detect by the symbol
+ * pbr_msaa_rasterize. */
+typedef struct pbr_msaa_surface {
+    uint64_t* visibility; /* DEVICE, 8-byte aligned: 4 planes, sample-major, of (row_end - row_begin) rows of row_stride
+                           * words: word (s, y - row_begin, x) = (bits(z) << 32) | triangle ordinal of the fragment
+                           * sample s of pixel (x, y) shows, all ones for none. The high word is the sample's depth. */
+    int64_t row_stride;   /* words; >= width */
+} pbr_msaa_surface;
+
+/* Vertex stage, setup and per-sample coverage of `draws` into `surface`, asynchronously on `stream`. The call first
+ * sets all 4 * rows * row_stride words of the surface to all ones, the padding words included. `flags` must be 0:
+ * PBR_RASTER_CLIP_NEAR and PBR_RASTER_ALPHA_TEST return PBR_ERR_UNSUPPORTED; unknown bits and bit 1 are
+ * PBR_ERR_INVALID_ARGUMENT, as are a NULL surface, a NULL or misaligned `visibility` and a row_stride below the width.
+ * Otherwise arguments, readiness and stream rules are pbr_rasterize's, and the result is as independent of execution
+ * order and of the band. pbr_last_raster_stats keeps its meanings, except that `fragments` counts (triangle, sample)
+ * pairs. */
+int pbr_msaa_rasterize(pbr_context* ctx, const pbr_draw* draws, int32_t n_draws, const pbr_raster_view* view,
+                       uint32_t flags, const pbr_msaa_surface* surface, void* stream);
+
+/* Slot `slot` (0 .. 3, else PBR_ERR_INVALID_ARGUMENT) of every pixel of the band out of `surface`, into `targets` as
+ * pbr_rasterize writes them: the fragment's attributes at the pixel centre, its draw's material and, in the optional
+ * depth plane, the high word of the key of the slot's lowest sample. A background fragment, and a slot the pixel does
+ * not have, get the background planes, PBR_MATERIAL_NONE and depth 1. Every pixel of the band is written in every
+ * call. `owner` (DEVICE, may be NULL; owner_row_stride bytes per row, >= width) receives per pixel
+ * sum over s of slot(s) << 2s; it is the same for every slot. The call runs the vertex stage again, so `draws` and `view`
+ * must be those of the pbr_msaa_rasterize call that filled the surface (a key whose ordinal is past the list is taken
+ * as background). `flags` as pbr_msaa_rasterize. The counters of pbr_last_raster_stats stay those of the stream's last
+ * rasterising call. */
+int pbr_msaa_fragments(pbr_context* ctx, const pbr_draw* draws, int32_t n_draws, const pbr_raster_view* view,
+                       uint32_t flags, const pbr_msaa_surface* surface, int32_t slot, const pbr_raster_targets* targets,
+                       uint8_t* owner, int64_t owner_row_stride, void* stream);
+
+typedef struct pbr_msaa_stats {
+    int64_t slot_pixels[4]; /* pixels of the band in which slot k exists; [0] is the band's pixel count. A caller shades
+                             * slots 0 .. the last k with slot_pixels[k] > 0 */
+} pbr_msaa_stats;
+
+/* Computed by every pbr_msaa_fragments call, whatever its slot (synchronises `stream`, like pbr_last_raster_stats);
+ * zeros after any other rasterising call and when the context has not rasterised on that stream. */
+int pbr_last_msaa_stats(pbr_context* ctx, pbr_msaa_stats* out, void* stream);
+
+/* The shaded slots of a frame, DEVICE memory. */
+typedef struct pbr_msaa_resolve_source {
+    const float* slots[4];    /* RGBA32F frames, 4-byte aligned (all 16-byte aligned: one access per pixel and frame);
+                               * slots[k] is read only for k < n_slots and may be NULL past it */
+    int64_t slot_row_stride;  /* pixels, >= width; one stride for every slot frame */
+    int32_t n_slots;          /* 1 .. 4 */
+    const uint8_t* owner;     /* the owner plane pbr_msaa_fragments wrote */
+    int64_t owner_row_stride; /* bytes, >= width */
+} pbr_msaa_resolve_source;
+
+/* The multisample resolve into `dst` (out, out_row_stride and format are used, as by pbr_blend_layer), width x height
+ * pixels, asynchronously on `stream`. With c_s the pixel of the slot frame that owns sample s, (owner >> 2s) & 3 -- 0 in
+ * every channel when that slot is >= n_slots -- per channel, alpha included:
+ * RGBA32F: out = ((c_0 + c_1) + (c_2 + c_3)) * 0.25f, each operation rounded once; pairwise, so a pixel whose samples
+ * all belong to one fragment gets that fragment's colour bit for bit. RGBA8_UNORM: each sample first holds
+ * unorm8(clamp(c_s)), as a UNORM8 multisampled target stores it (the clamp of pbr_blend_layer, NaN -> 0; the
+ * FLOAT -> UNORM rule of pbr_output_format); d_s = (float)byte / 255.0f, the same expression, and the rule again.
+ * Every pixel of the rectangle is written. Not a shading pass: the pass statistics stay. */
+int pbr_msaa_resolve(pbr_context* ctx, const pbr_msaa_resolve_source* source, const pbr_frame_desc* dst, int32_t width,
+                     int32_t height, void* stream);
+
 /* ---- Host G-buffer fill (replaces the VS + rasteriser front-end, Default.hlsl:22-45) ---------- */
 
 typedef enum pbr_scene_kind {

@@ -444,9 +444,37 @@ class ShadingContext {
         Check(pbr_blend_layer(ctx_, &source, &dst, width, height, stream), "pbr_blend_layer");
     }
 
+    // Four samples per pixel. MsaaRasterize: vertex stage, setup and per-sample coverage of
+    // `draws` into the caller's `surface` (4 sample-major planes of the band's rows; set to all ones first).
+    // MsaaFragments: slot 0 .. 3 of every pixel out of the surface into `attrs` (attributes at the pixel centre) and the
+    // optional `depth` and `owner` planes; `draws` and `view` are those of MsaaRasterize. `flags` must be 0.
+    void MsaaRasterize(const std::vector<pbr_draw>& draws, const pbr_raster_view& view, const pbr_msaa_surface& surface,
+                       hipStream_t stream = nullptr, uint32_t flags = 0) {
+        Check(pbr_msaa_rasterize(ctx_, draws.data(), static_cast<int32_t>(draws.size()), &view, flags, &surface, stream),
+              "pbr_msaa_rasterize");
+    }
+    void MsaaFragments(const std::vector<pbr_draw>& draws, const pbr_raster_view& view, const pbr_msaa_surface& surface,
+                       int32_t slot, DeviceAttributes& attrs, float* depth = nullptr, uint8_t* owner = nullptr,
+                       int64_t owner_row_stride = 0, hipStream_t stream = nullptr, uint32_t flags = 0) {
+        const pbr_raster_targets t = RasterTargets(view, attrs, depth);
+        Check(pbr_msaa_fragments(ctx_, draws.data(), static_cast<int32_t>(draws.size()), &view, flags, &surface, slot, &t,
+                                 owner, owner_row_stride, stream), "pbr_msaa_fragments");
+    }
+    // The band's pixels in which slot 0 .. 3 exists, counted by the last MsaaFragments on `stream` (synchronises it).
+    pbr_msaa_stats LastMsaaStats(hipStream_t stream = nullptr) {
+        pbr_msaa_stats s;
+        Check(pbr_last_msaa_stats(ctx_, &s, stream), "pbr_last_msaa_stats");
+        return s;
+    }
+    // The multisample resolve of the shaded slot frames through the owner plane into `dst` (pbr_msaa_resolve).
+    void MsaaResolve(const pbr_msaa_resolve_source& source, const pbr_frame_desc& dst, int32_t width, int32_t height,
+                     hipStream_t stream = nullptr) {
+        Check(pbr_msaa_resolve(ctx_, &source, &dst, width, height, stream), "pbr_msaa_resolve");
+    }
+
   private:
-    void Rasterize(const std::vector<pbr_draw>& draws, const pbr_raster_view& view, DeviceAttributes& attrs, float* depth,
-                   hipStream_t stream, uint32_t flags, const pbr_raster_layer* layer) {
+    // The planes of `attrs`' band of `view` as the targets of a rasterising call.
+    static pbr_raster_targets RasterTargets(const pbr_raster_view& view, DeviceAttributes& attrs, float* depth) {
         const pbr_attributes_soa band = attrs.Band(view.row_begin, view.row_end);
         pbr_raster_targets t;
         std::memset(&t, 0, sizeof t);
@@ -461,6 +489,11 @@ class ShadingContext {
         t.material = const_cast<uint16_t*>(band.material);
         t.depth = depth;
         t.row_stride = band.row_stride;
+        return t;
+    }
+    void Rasterize(const std::vector<pbr_draw>& draws, const pbr_raster_view& view, DeviceAttributes& attrs, float* depth,
+                   hipStream_t stream, uint32_t flags, const pbr_raster_layer* layer) {
+        const pbr_raster_targets t = RasterTargets(view, attrs, depth);
         if (layer)
             Check(pbr_rasterize_layer(ctx_, draws.data(), static_cast<int32_t>(draws.size()), &view, &t, flags, layer,
                                       stream), "pbr_rasterize_layer");

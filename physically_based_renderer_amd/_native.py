@@ -294,6 +294,31 @@ class BlendSource(ctypes.Structure):
     ]
 
 
+class MsaaSurface(ctypes.Structure):
+    """pbr_msaa_surface: the caller-owned visibility words of a multisampled band, 4 sample-major planes."""
+    _fields_ = [
+        ("visibility", ctypes.c_void_p),
+        ("row_stride", ctypes.c_int64),
+    ]
+
+
+class MsaaStats(ctypes.Structure):
+    _fields_ = [
+        ("slot_pixels", ctypes.c_int64 * 4),
+    ]
+
+
+class MsaaResolveSource(ctypes.Structure):
+    """pbr_msaa_resolve_source: the shaded slot frames and the owner plane for pbr_msaa_resolve."""
+    _fields_ = [
+        ("slots", ctypes.c_void_p * 4),
+        ("slot_row_stride", ctypes.c_int64),
+        ("n_slots", ctypes.c_int32),
+        ("owner", ctypes.c_void_p),
+        ("owner_row_stride", ctypes.c_int64),
+    ]
+
+
 class PassStats(ctypes.Structure):
     """pbr_pass_stats: statistics of the last shading pass."""
     _fields_ = [
@@ -368,6 +393,16 @@ SIGNATURES = {
                                                    ctypes.c_void_p]),
     "pbr_blend_layer": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(BlendSource), ctypes.POINTER(FrameDesc),
                                        ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),
+    "pbr_msaa_rasterize": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(DrawDesc), ctypes.c_int32,
+                                          ctypes.POINTER(RasterView), ctypes.c_uint32, ctypes.POINTER(MsaaSurface),
+                                          ctypes.c_void_p]),
+    "pbr_msaa_fragments": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(DrawDesc), ctypes.c_int32,
+                                          ctypes.POINTER(RasterView), ctypes.c_uint32, ctypes.POINTER(MsaaSurface),
+                                          ctypes.c_int32, ctypes.POINTER(RasterTargets), ctypes.c_void_p, ctypes.c_int64,
+                                          ctypes.c_void_p]),
+    "pbr_last_msaa_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(MsaaStats), ctypes.c_void_p]),
+    "pbr_msaa_resolve": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(MsaaResolveSource), ctypes.POINTER(FrameDesc),
+                                        ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),
     "pbr_attributes_fill": (ctypes.c_int64, [ctypes.POINTER(SceneDesc), ctypes.c_int32, ctypes.c_int32,
                                              ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.c_int64,
                                              ctypes.c_int32]),

@@ -122,7 +122,8 @@ struct RasterVertex {
 // their slots.
 enum RasterCounter { kRasterLarge = 0, kRasterCulled, kRasterZeroArea, kRasterNear, kRasterGuard, kRasterFragments,
                      kRasterClipped, kRasterClipPieces, kRasterAlphaTested, kRasterAlphaDiscarded,
-                     kRasterLayerFragments, kRasterCounters = 11 };
+                     kRasterLayerFragments, kRasterSlotPixels /* four words: pbr_msaa_stats */,
+                     kRasterCounters = kRasterSlotPixels + 4 };
 
 struct RasterArgs {
     const float* vertices;    // the mesh set: 14 floats per vertex
@@ -188,6 +189,39 @@ struct BlendArgs {
 };
 constexpr int kBlendRgba32f = 0, kBlendRgba8 = 1;
 hipError_t launch_blend_layer(const BlendArgs& a, hipStream_t stream);
+
+// ---- Four samples per pixel (raster.h, msaa_resolve.h; pbr_msaa_*) -------------------------
+// A multisampled call's arguments: those of a rasterisation (r.vis is not used; r.plane, r.material, r.depth and
+// r.stride only by the fragments stage) and the caller's visibility surface: four planes, sample-major, of
+// (r.row_end - r.row_begin) rows of vis_stride words.
+struct MsaaArgs {
+    RasterArgs r;
+    unsigned long long* vis;
+    int64_t vis_stride;    // words per row, >= r.width
+    int slot;              // the fragments stage: 0 .. 3
+    uint8_t* owner;        // the fragments stage: the owner plane, or nullptr
+    int64_t owner_stride;  // bytes
+};
+// The sample-coverage instantiations of the setup and large-triangle stages, and the fragments stage that takes the
+// resolve's place: one launch each (none when it has nothing to do).
+hipError_t launch_msaa_setup(const MsaaArgs& a, hipStream_t stream);
+hipError_t launch_msaa_large(const MsaaArgs& a, hipStream_t stream);
+hipError_t launch_msaa_fragments(const MsaaArgs& a, hipStream_t stream);
+
+// The multisample resolve of up to four shaded slot frames through the owner plane (pbr_msaa_resolve).
+struct MsaaResolveArgs {
+    const float* slots[4];  // RGBA32F frames; slots[k] is read only for k < n_slots
+    int64_t slot_stride;    // pixels
+    int n_slots;            // 1 .. 4
+    const uint8_t* owner;
+    int64_t owner_stride;   // bytes
+    void* out;              // RGBA32F or RGBA8
+    int64_t out_stride;     // pixels
+    int width, height;
+    int format;  // kBlendRgba32f / kBlendRgba8
+    bool vec;    // every slot frame and (RGBA32F) out 16-byte aligned: one 16-byte access per pixel and frame
+};
+hipError_t launch_msaa_resolve(const MsaaResolveArgs& a, hipStream_t stream);
 
 // PBR_DEBUG_BOUNDS builds only (pbr_debug_bounds.h): point this unit's kernels at the device's bounds-flag buffer.
 hipError_t debug_bounds_publish_frontend(uint32_t* buf);

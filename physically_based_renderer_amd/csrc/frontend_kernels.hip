@@ -12,6 +12,7 @@
 #include "material_resolve.h"
 #include "raster.h"
 #include "blend_layer.h"
+#include "msaa_resolve.h"
 
 namespace pbr {
 

@@ -382,14 +382,34 @@ int pbr_set_meshes(pbr_context* ctx, const pbr_mesh_desc* meshes, int32_t n_mesh
 
 namespace {
 
-// pbr_rasterize (flags 0), pbr_rasterize_flags and, with `layer`, pbr_rasterize_layer. `marks` (development, pbr_debug_rasterize_timed): six events
+// What a multisampled call adds to a rasterisation: the caller's surface and, for pbr_msaa_fragments (slot >= 0), the
+// slot and the owner plane. slot < 0: pbr_msaa_rasterize, which has no targets.
+struct MsaaCall {
+    const pbr_msaa_surface* surface;
+    int32_t slot;
+    uint8_t* owner;
+    int64_t owner_stride;
+};
+
+// pbr_rasterize (flags 0), pbr_rasterize_flags, with `layer` pbr_rasterize_layer, and with `msaa` pbr_msaa_rasterize and
+// pbr_msaa_fragments. `marks` (development, pbr_debug_rasterize_timed): six events
 // recorded around the five stages -- clears and table upload, vertex transform, setup with the small triangles'
 // coverage, large triangles, resolve.
 int rasterize_impl(pbr_context* ctx, const pbr_draw* draws, int32_t n_draws, const pbr_raster_view* view,
                    const pbr_raster_targets* tg, uint32_t flags, void* stream, hipEvent_t* marks,
-                   const pbr_raster_layer* layer = nullptr) {
-    if (!ctx || !view || !tg || n_draws < 0 || (n_draws > 0 && !draws)) return PBR_ERR_INVALID_ARGUMENT;
+                   const pbr_raster_layer* layer = nullptr, const MsaaCall* msaa = nullptr) {
+    const bool coverage_only = msaa && msaa->slot < 0;  // pbr_msaa_rasterize: nothing but the surface is written
+    if (!ctx || !view || (!tg && !coverage_only) || n_draws < 0 || (n_draws > 0 && !draws))
+        return PBR_ERR_INVALID_ARGUMENT;
     if (flags & ~(uint32_t)(PBR_RASTER_CLIP_NEAR | PBR_RASTER_ALPHA_TEST)) return PBR_ERR_INVALID_ARGUMENT;
+    if (msaa) {  // no clip piece as a fragment identity and no per-pixel alpha test under multisampling yet
+        if (flags != 0u) return PBR_ERR_UNSUPPORTED;
+        const pbr_msaa_surface* sf = msaa->surface;
+        if (!sf || !sf->visibility || !aligned(sf->visibility, 8) || sf->row_stride < view->width)
+            return PBR_ERR_INVALID_ARGUMENT;
+        if (!coverage_only && (msaa->slot > 3 || (msaa->owner && msaa->owner_stride < view->width)))
+            return PBR_ERR_INVALID_ARGUMENT;
+    }
     if (layer) {  // the transparent PSO runs no alpha test; the layer's planes and the depth plane are required
         if (flags & PBR_RASTER_ALPHA_TEST) return PBR_ERR_INVALID_ARGUMENT;
         if (!layer->depth_in || !layer->prim_out || !tg->depth) return PBR_ERR_INVALID_ARGUMENT;
@@ -401,21 +421,24 @@ int rasterize_impl(pbr_context* ctx, const pbr_draw* draws, int32_t n_draws, con
         return PBR_ERR_INVALID_ARGUMENT;
     if (view->row_begin < 0 || view->row_begin > view->row_end || view->row_end > view->height)
         return PBR_ERR_INVALID_ARGUMENT;
-    if (tg->row_stride < view->width) return PBR_ERR_INVALID_ARGUMENT;
+    if (tg && tg->row_stride < view->width) return PBR_ERR_INVALID_ARGUMENT;
     for (int32_t i = 0; i < n_draws; ++i) {
         const pbr_draw& d = draws[i];
         if (d.mesh < 0 || d.first_index < 0 || d.index_count < 0 || d.index_count % 3 != 0 || d.cull > 1)
             return PBR_ERR_INVALID_ARGUMENT;
     }
     pbr::RasterArgs a{};
-    a.vec = (tg->row_stride % 2) == 0;
-    if (!planes_ok(tg->planes, 14, 4, a.vec)) return PBR_ERR_INVALID_ARGUMENT;
-    std::copy(tg->planes, tg->planes + 14, a.plane);
-    if (!tg->material || !aligned(tg->material, 2)) return PBR_ERR_INVALID_ARGUMENT;
-    if (tg->depth && !aligned(tg->depth, 4)) return PBR_ERR_INVALID_ARGUMENT;
-    a.material = tg->material;
-    a.depth = tg->depth;
-    a.vec = a.vec && aligned(tg->material, 4) && aligned(tg->depth, 8);
+    if (tg) {
+        a.vec = (tg->row_stride % 2) == 0;
+        if (!planes_ok(tg->planes, 14, 4, a.vec)) return PBR_ERR_INVALID_ARGUMENT;
+        std::copy(tg->planes, tg->planes + 14, a.plane);
+        if (!tg->material || !aligned(tg->material, 2)) return PBR_ERR_INVALID_ARGUMENT;
+        if (tg->depth && !aligned(tg->depth, 4)) return PBR_ERR_INVALID_ARGUMENT;
+        a.material = tg->material;
+        a.depth = tg->depth;
+        a.vec = a.vec && aligned(tg->material, 4) && aligned(tg->depth, 8);
+        a.stride = tg->row_stride;
+    }
     if (layer) {
         a.peel = true;
         a.depth_in = layer->depth_in;
@@ -423,7 +446,6 @@ int rasterize_impl(pbr_context* ctx, const pbr_draw* draws, int32_t n_draws, con
         a.prim_out = layer->prim_out;
         a.vec = a.vec && aligned(layer->prim_out, 8);
     }
-    a.stride = tg->row_stride;
     a.width = view->width;
     a.height = view->height;
     a.row_begin = view->row_begin;
@@ -503,9 +525,11 @@ int rasterize_impl(pbr_context* ctx, const pbr_draw* draws, int32_t n_draws, con
     const size_t off_records = off_table + align_up(table_bytes, 256);
     const size_t off_large = off_records + align_up(sizeof(pbr::RasterVertex) * (size_t)n_records, 256);
     const size_t off_vis = off_large + align_up(sizeof(uint2) * n_large, 256);
-    const size_t vis_bytes = sizeof(unsigned long long) * (size_t)band_h * (size_t)view->width;
+    // (a multisampled call's visibility words are the caller's surface)
+    const size_t vis_bytes = msaa ? 0 : sizeof(unsigned long long) * (size_t)band_h * (size_t)view->width;
     const size_t off_posh = off_vis + align_up(vis_bytes, 256);
     const size_t need = clip_near ? off_posh + sizeof(float4) * (size_t)n_records : off_vis + vis_bytes;
+    const bool regrown = need > rs.capacity;
     if (need > rs.capacity) {  // grown in stream order: the stream's earlier rasterisations finish with the old block
         if (rs.d) {
             e = hipFreeAsync(rs.d, s);
@@ -550,11 +574,49 @@ int rasterize_impl(pbr_context* ctx, const pbr_draw* draws, int32_t n_draws, con
     if (e != hipSuccess) return fail_hip(ctx, e, "pbr_rasterize order");
     auto mark = [&](int i) { return marks ? hipEventRecord(marks[i], s) : hipSuccess; };
     (void)mark(0);
-    e = hipMemsetAsync(rs.d, 0, sizeof(unsigned long long) * pbr::kRasterCounters, s);
+    // pbr_msaa_fragments counts slot_pixels only: the other counters stay those of the stream's last rasterising call
+    // (zeros when this call is the stream's first, or found the scratch too small).
+    const bool keep_counters = msaa && !coverage_only && rs.ran && !regrown;
+    if (keep_counters)
+        e = hipMemsetAsync(rs.d_counters + pbr::kRasterSlotPixels, 0, sizeof(unsigned long long) * 4, s);
+    else
+        e = hipMemsetAsync(rs.d, 0, sizeof(unsigned long long) * pbr::kRasterCounters, s);
     if (e == hipSuccess) e = hipMemcpyAsync(rs.d + off_table, rs.h, table_bytes, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipEventRecord(rs.staged, s);
     if (e != hipSuccess) return fail_hip(ctx, e, "pbr_rasterize upload");
     rs.staged_pending = true;
+    if (msaa) {
+        pbr::MsaaArgs m{};
+        a.vis = nullptr;
+        m.r = a;
+        m.vis = reinterpret_cast<unsigned long long*>(msaa->surface->visibility);
+        m.vis_stride = msaa->surface->row_stride;
+        m.slot = msaa->slot;
+        m.owner = msaa->owner;
+        m.owner_stride = msaa->owner_stride;
+        if (coverage_only) {
+            e = hipMemsetAsync(m.vis, 0xFF, sizeof(unsigned long long) * 4 * (size_t)band_h * (size_t)m.vis_stride, s);
+            if (e != hipSuccess) return fail_hip(ctx, e, "pbr_msaa_rasterize clear");
+        }
+        e = pbr::launch_raster_vertices(a, s);
+        if (e != hipSuccess) return fail_hip(ctx, e, "raster_vertex_kernel launch", PBR_ERR_LAUNCH);
+        if (coverage_only) {
+            e = pbr::launch_msaa_setup(m, s);
+            if (e != hipSuccess) return fail_hip(ctx, e, "raster_setup_msaa_kernel launch", PBR_ERR_LAUNCH);
+            e = pbr::launch_msaa_large(m, s);
+            if (e != hipSuccess) return fail_hip(ctx, e, "raster_large_msaa_kernel launch", PBR_ERR_LAUNCH);
+        } else {
+            // slot 0 exists in every pixel: its count is the band's (at most 2^30, the low half of the cleared word)
+            e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(rs.d_counters + pbr::kRasterSlotPixels),
+                                  band_h * view->width, 1, s);
+            if (e != hipSuccess) return fail_hip(ctx, e, "pbr_msaa_fragments count");
+            e = pbr::launch_msaa_fragments(m, s);
+            if (e != hipSuccess) return fail_hip(ctx, e, "raster_fragments_msaa_kernel launch", PBR_ERR_LAUNCH);
+        }
+        if (!keep_counters) rs.triangles = (int64_t)n_tris;
+        rs.ran = true;
+        return after_launch(ctx, si, s, "pbr_msaa record");
+    }
     e = hipMemsetAsync(a.vis, 0xFF, vis_bytes, s);
     if (e != hipSuccess) return fail_hip(ctx, e, "pbr_rasterize clear");
     (void)mark(1);
@@ -671,6 +733,64 @@ int pbr_last_raster_layer_stats(pbr_context* ctx, pbr_raster_layer_stats* out, v
     if (const int rc = read_raster_counters(ctx, stream, h, &triangles, &ran, "pbr_last_raster_layer_stats")) return rc;
     out->layer_fragments = (int64_t)h[pbr::kRasterLayerFragments];
     return PBR_OK;
+}
+
+int pbr_msaa_rasterize(pbr_context* ctx, const pbr_draw* draws, int32_t n_draws, const pbr_raster_view* view,
+                       uint32_t flags, const pbr_msaa_surface* surface, void* stream) {
+    const MsaaCall call{surface, -1, nullptr, 0};
+    return rasterize_impl(ctx, draws, n_draws, view, nullptr, flags, stream, nullptr, nullptr, &call);
+}
+
+int pbr_msaa_fragments(pbr_context* ctx, const pbr_draw* draws, int32_t n_draws, const pbr_raster_view* view,
+                       uint32_t flags, const pbr_msaa_surface* surface, int32_t slot, const pbr_raster_targets* targets,
+                       uint8_t* owner, int64_t owner_row_stride, void* stream) {
+    if (slot < 0 || slot > 3) return PBR_ERR_INVALID_ARGUMENT;
+    const MsaaCall call{surface, slot, owner, owner_row_stride};
+    return rasterize_impl(ctx, draws, n_draws, view, targets, flags, stream, nullptr, nullptr, &call);
+}
+
+int pbr_last_msaa_stats(pbr_context* ctx, pbr_msaa_stats* out, void* stream) {
+    if (!ctx || !out) return PBR_ERR_INVALID_ARGUMENT;
+    *out = pbr_msaa_stats{};
+    unsigned long long h[pbr::kRasterCounters] = {};  // every other call clears them: zeros unless it was a fragments call
+    int64_t triangles = 0;
+    bool ran = false;
+    if (const int rc = read_raster_counters(ctx, stream, h, &triangles, &ran, "pbr_last_msaa_stats")) return rc;
+    for (int k = 0; k < 4; ++k) out->slot_pixels[k] = (int64_t)h[pbr::kRasterSlotPixels + k];
+    return PBR_OK;
+}
+
+// The multisample resolve of the shaded slots of a frame (msaa_resolve.h).
+int pbr_msaa_resolve(pbr_context* ctx, const pbr_msaa_resolve_source* src, const pbr_frame_desc* dst, int32_t width,
+                     int32_t height, void* stream) {
+    if (!ctx || !src || !dst || width < 0 || height < 0) return PBR_ERR_INVALID_ARGUMENT;
+    if (dst->format != PBR_OUTPUT_RGBA32F && dst->format != PBR_OUTPUT_RGBA8_UNORM) return PBR_ERR_INVALID_ARGUMENT;
+    if (src->n_slots < 1 || src->n_slots > 4 || !src->owner || !dst->out || !aligned(dst->out, 4))
+        return PBR_ERR_INVALID_ARGUMENT;
+    if (src->slot_row_stride < width || src->owner_row_stride < width || dst->out_row_stride < width)
+        return PBR_ERR_INVALID_ARGUMENT;
+    pbr::MsaaResolveArgs a{};
+    a.format = dst->format == PBR_OUTPUT_RGBA8_UNORM ? pbr::kBlendRgba8 : pbr::kBlendRgba32f;
+    a.vec = a.format == pbr::kBlendRgba8 || aligned(dst->out, 16);
+    for (int k = 0; k < src->n_slots; ++k) {
+        if (!src->slots[k] || !aligned(src->slots[k], 4)) return PBR_ERR_INVALID_ARGUMENT;
+        a.slots[k] = src->slots[k];
+        a.vec = a.vec && aligned(src->slots[k], 16);
+    }
+    Entry en(ctx);
+    if (width == 0 || height == 0) return PBR_OK;  // an empty frame: nothing is read or written
+    a.slot_stride = src->slot_row_stride;
+    a.n_slots = src->n_slots;
+    a.owner = src->owner;
+    a.owner_stride = src->owner_row_stride;
+    a.out = dst->out;
+    a.out_stride = dst->out_row_stride;
+    a.width = width;
+    a.height = height;
+    // Not a shading pass and a reader of no context resource, as pbr_blend_layer.
+    if (const int rc = en.device(stream)) return rc;
+    const hipError_t e = pbr::launch_msaa_resolve(a, en.s);
+    return e == hipSuccess ? PBR_OK : fail_hip(ctx, e, "msaa_resolve_kernel launch", PBR_ERR_LAUNCH);
 }
 
 // The transparent PSO's output-merger blend of a shaded layer over the frame (blend_layer.h).

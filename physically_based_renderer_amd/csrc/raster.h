@@ -46,6 +46,10 @@
 // (ordinal << 32) | bits(z), so the atomicMin keeps the earliest eligible fragment in submission order -- the next
 // fragment the D3D depth test would accept. The resolve writes that fragment's attributes, its z as the new depth and
 // its ordinal + 1 as the next floor; a pixel without one keeps the incoming depth and gets the floor 0xFFFFFFFF.
+//
+// Four samples per pixel (pbr_msaa_rasterize, pbr_msaa_fragments) are kernels of their own at
+// the end of this file -- raster_setup_msaa_kernel, raster_large_msaa_kernel, raster_fragments_msaa_kernel -- launched
+// by the multisampled calls only; the kernels of every other call are what they were, instruction for instruction.
 #pragma once
 
 #include "pbr_device_math.h"
@@ -1059,6 +1063,282 @@ hipError_t launch_raster_resolve(const RasterArgs& a, hipStream_t stream) {
     } else {
         hipLaunchKernelGGL((raster_resolve_kernel<false, false, false>), grid, dim3(256), 0, stream, a);
     }
+    return hipGetLastError();
+}
+
+// ---- Four samples per pixel (step 7b; pbr_msaa_rasterize, pbr_msaa_fragments) -------------------------------------
+// Kernels of their own beside the 1x ones (as raster_setup_clip_kernel is beside raster_setup_kernel), built from the
+// same helpers: the 1x kernels above are not touched. Coverage and depth are steps 5-6 at the four sample points of a
+// pixel, D3D's standard pattern in 1/16 pixel, which lies on the 1/256 grid; visibility is step 7's key lowered by
+// atomicMin into one word per (sample, pixel) of the caller's surface, sample-major. The fragments stage takes the
+// resolve's place: the samples of a pixel with the same triangle are one fragment, numbered as slots by their lowest
+// sample; slot k's attributes are step 8 at the pixel centre, whether or not the centre is covered.
+namespace raster {
+
+constexpr int kSamples = 4;
+constexpr int kSampleReach = 96;  // no sample is further from its pixel's centre, in subpixels, along either axis
+
+// Sample s of a pixel is at (256 x + 128 + sample_dx(s), 256 y + 128 + sample_dy(s)):
+// (-2, -6), (6, -2), (-6, 2), (2, 6) sixteenths of a pixel.
+__device__ __forceinline__ int sample_dx(int s) { return s == 0 ? -32 : (s == 1 ? 96 : (s == 2 ? -96 : 32)); }
+__device__ __forceinline__ int sample_dy(int s) { return s == 0 ? -96 : (s == 1 ? -32 : (s == 2 ? 32 : 96)); }
+
+// edge_at for any point of the subpixel grid.
+__device__ __forceinline__ long long edge_at_point(const Edges& e, int k, int px, int py) {
+    return (long long)e.dx[k] * (long long)(py - e.ya[k]) - (long long)e.dy[k] * (long long)(px - e.xa[k]);
+}
+
+// tri_box for sample points: the pixels that can have a sample inside the triangle's bounding box, clipped to the
+// band. Conservative: every point within kSampleReach of the centre counts, whether a sample sits there or not.
+__device__ __forceinline__ bool tri_box_samples(const RasterArgs& a, const Tri& s, Box& b) {
+    const int minx = min(s.X[0], min(s.X[1], s.X[2])), maxx = max(s.X[0], max(s.X[1], s.X[2]));
+    const int miny = min(s.Y[0], min(s.Y[1], s.Y[2])), maxy = max(s.Y[0], max(s.Y[1], s.Y[2]));
+    // 256 p + 128 + 96 >= min and 256 p + 128 - 96 <= max
+    b.x0 = max((minx - (128 + kSampleReach) + 255) >> 8, 0);
+    b.x1 = min((maxx - (128 - kSampleReach)) >> 8, a.width - 1);
+    b.y0 = max((miny - (128 + kSampleReach) + 255) >> 8, a.row_begin);
+    b.y1 = min((maxy - (128 - kSampleReach)) >> 8, a.row_end - 1);
+    return b.x0 <= b.x1 && b.y0 <= b.y1;
+}
+
+// raster_pixel for the four samples of pixel (x, y); the sample fragments that exist (0 .. 4).
+__device__ __forceinline__ uint32_t raster_pixel_samples(const MsaaArgs& m, const Tri& s, const Edges& e,
+                                                         const float z[3], uint32_t prim, int x, int y) {
+    const RasterArgs& a = m.r;
+    const int band_h = a.row_end - a.row_begin;
+    const int64_t plane = (int64_t)band_h * m.vis_stride;
+    const int64_t i = PBR_BOUNDS_PIXEL((int64_t)(y - a.row_begin) * m.vis_stride + x, a.width, band_h, m.vis_stride, 1,
+                                       kBoundsRaster);
+    uint32_t frags = 0;
+#pragma unroll
+    for (int sm = 0; sm < kSamples; ++sm) {
+        const int px = 256 * x + 128 + sample_dx(sm), py = 256 * y + 128 + sample_dy(sm);
+        const long long E[3] = {edge_at_point(e, 0, px, py), edge_at_point(e, 1, px, py), edge_at_point(e, 2, px, py)};
+        if (!covered(e, E)) continue;
+        float l[3];
+        barycentrics(E, s.A, l);
+        const float zf = interpolate_z(l, z);
+        if (!(zf >= 0.0f && zf < 1.0f)) continue;
+        const unsigned long long key = ((unsigned long long)__float_as_uint(zf) << 32) | (unsigned long long)prim;
+        atomicMin(m.vis + sm * plane + i, key);
+        ++frags;
+    }
+    return frags;
+}
+
+}  // namespace raster
+
+// Stage 2 for samples: raster_setup_kernel's flow with the sample box: a triangle whose box of pixels with reachable
+// samples holds at most kSmallPixels pixels is rasterised by its lane (at most 4 kSmallPixels sample tests), the others
+// are listed. A triangle that covers a sample but no pixel centre has an empty centre box and a non-empty sample box.
+__global__ __launch_bounds__(256) void raster_setup_msaa_kernel(const MsaaArgs m) {
+    using namespace raster;
+    const RasterArgs& a = m.r;
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    const bool valid = t < a.n_tris;
+    Tri s;
+    TriStatus st = kTriZeroArea;
+    if (valid) st = tri_setup(a, t, s);
+    count_ballot(a.counters + kRasterCulled, valid && st == kTriCulled);
+    count_ballot(a.counters + kRasterZeroArea, valid && st == kTriZeroArea);
+    count_ballot(a.counters + kRasterNear, valid && st == kTriNear);
+    count_ballot(a.counters + kRasterGuard, valid && st == kTriGuard);
+    Box b{0, -1, 0, -1};
+    const bool draw = valid && st == kTriDraw && tri_box_samples(a, s, b);
+    const long long npix = draw ? (long long)(b.x1 - b.x0 + 1) * (long long)(b.y1 - b.y0 + 1) : 0;
+    const bool small = draw && npix <= kSmallPixels, large = draw && !small;
+    uint32_t frags = 0;
+    if (small) {
+        Edges e;
+        tri_edges(s, e);
+        float z[3];
+        load_z(a, s, z);
+        for (int y = b.y0; y <= b.y1; ++y)
+            for (int x = b.x0; x <= b.x1; ++x) frags += raster_pixel_samples(m, s, e, z, t, x, y);
+    }
+    count_wave(a.counters + kRasterFragments, frags);
+    append_large(a, large, b, t, 0u, (int64_t)a.n_tris);
+}
+
+// Stage 3 for samples: raster_large_kernel<false, false, false>'s flow over the sample box. A block is skipped when
+// some edge function is negative at the four corners of the rectangle that holds every sample point of the block (the
+// block's corner pixel centres moved outwards by kSampleReach): linear, so negative at every sample of the block.
+__global__ __launch_bounds__(256) void raster_large_msaa_kernel(const MsaaArgs m) {
+    using namespace raster;
+    const RasterArgs& a = m.r;
+    const unsigned long long listed = a.counters[kRasterLarge];
+    const uint32_t slots = a.n_tris;
+    const uint32_t n_large = listed < (unsigned long long)slots ? (uint32_t)listed : slots;
+    uint32_t frags = 0;
+    for (uint32_t i = blockIdx.x; i < n_large; i += gridDim.x) {
+        const uint2 entry = a.large[PBR_BOUNDS((int64_t)i, (int64_t)slots, kBoundsRaster)];
+        if (blockIdx.y >= entry.y) continue;
+        const uint32_t t = entry.x;
+        Tri s;
+        Box b;
+        if (tri_setup(a, t, s) != kTriDraw || !tri_box_samples(a, s, b)) continue;  // never: the setup kernel listed it
+        const uint32_t nbx = (uint32_t)(b.x1 - b.x0) / kBlockW + 1u, nby = (uint32_t)(b.y1 - b.y0) / kBlockH + 1u;
+        const uint32_t nb = nbx * nby;
+        if (blockIdx.y >= nb) continue;
+        Edges e;
+        tri_edges(s, e);
+        float z[3];
+        load_z(a, s, z);
+        for (uint32_t blk = blockIdx.y; blk < nb; blk += gridDim.y) {
+            const int X0 = b.x0 + (int)(blk % nbx) * kBlockW, Y0 = b.y0 + (int)(blk / nbx) * kBlockH;
+            const int X1 = min(X0 + kBlockW - 1, b.x1), Y1 = min(Y0 + kBlockH - 1, b.y1);
+            const int px0 = 256 * X0 + 128 - kSampleReach, px1 = 256 * X1 + 128 + kSampleReach;
+            const int py0 = 256 * Y0 + 128 - kSampleReach, py1 = 256 * Y1 + 128 + kSampleReach;
+            bool reject = false;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const long long mx = max(max(edge_at_point(e, k, px0, py0), edge_at_point(e, k, px1, py0)),
+                                         max(edge_at_point(e, k, px0, py1), edge_at_point(e, k, px1, py1)));
+                reject = reject || mx < 0;
+            }
+            if (reject) continue;
+            const int x = X0 + (int)(threadIdx.x & 63u), y = Y0 + (int)(threadIdx.x >> 6);
+            if (x <= X1 && y <= Y1) frags += raster_pixel_samples(m, s, e, z, t, x, y);
+        }
+    }
+    count_wave(a.counters + kRasterFragments, frags);
+}
+
+namespace raster {
+
+// One pixel of slot m.slot: the four keys, the slots and the owner byte; the slot's planes (step 8 at the pixel
+// centre with the triangle of the slot's lowest sample, the depth that sample's key carries) or, for a background
+// fragment or a slot the pixel does not have, step 9's. Returns the pixel's slot count (1 .. 4).
+__device__ __forceinline__ int fragments_pixel(const MsaaArgs& m, int x, int y, float out[14], uint32_t& material,
+                                               float& depth, uint32_t& owner) {
+    const RasterArgs& a = m.r;
+    const int band_h = a.row_end - a.row_begin;
+    const int64_t plane = (int64_t)band_h * m.vis_stride;
+    const int64_t i = PBR_BOUNDS_PIXEL((int64_t)(y - a.row_begin) * m.vis_stride + x, a.width, band_h, m.vis_stride, 1,
+                                       kBoundsRaster);
+    unsigned long long key[kSamples];
+#pragma unroll
+    for (int sm = 0; sm < kSamples; ++sm) key[sm] = m.vis[sm * plane + i];
+    // the low word names the fragment: a triangle's ordinal (below 2^32 - 1), or all ones for the background
+    const uint32_t id0 = (uint32_t)key[0], id1 = (uint32_t)key[1], id2 = (uint32_t)key[2], id3 = (uint32_t)key[3];
+    const int s1 = id1 == id0 ? 0 : 1;
+    int n = s1 + 1;
+    const int s2 = id2 == id0 ? 0 : (id2 == id1 ? s1 : n++);
+    const int s3 = id3 == id0 ? 0 : (id3 == id1 ? s1 : (id3 == id2 ? s2 : n++));
+    owner = (uint32_t)s1 << 2 | (uint32_t)s2 << 4 | (uint32_t)s3 << 6;
+    // the slot's lowest sample: slot k first appears at sample >= k
+    unsigned long long k64 = ~0ull;
+    if (m.slot == 0)
+        k64 = key[0];
+    else if (s1 == m.slot)
+        k64 = key[1];
+    else if (s2 == m.slot)
+        k64 = key[2];
+    else if (s3 == m.slot)
+        k64 = key[3];
+    Tri s;
+    // (a winner always sets up as drawn; an ordinal past the list -- a surface of another draw list -- is not followed)
+    if (k64 == ~0ull || (uint32_t)k64 >= a.n_tris || tri_setup(a, (uint32_t)k64, s) != kTriDraw) {
+        background_pixel(a, x, y, out, material, depth);
+        return n;
+    }
+    Edges e;
+    tri_edges(s, e);
+    const long long E[3] = {edge_at(e, 0, x, y), edge_at(e, 1, x, y), edge_at(e, 2, x, y)};
+    float l[3], p[3], q[3];
+    barycentrics(E, s.A, l);  // at the centre, inside the triangle or not: no clamp
+    const RasterVertex* r[3];
+#pragma unroll
+    for (int v = 0; v < 3; ++v) r[v] = a.records + PBR_BOUNDS((int64_t)s.rec[v], (int64_t)a.n_records, kBoundsRaster);
+    depth = __uint_as_float((uint32_t)(k64 >> 32));
+#pragma unroll
+    for (int v = 0; v < 3; ++v) p[v] = l[v] * r[v]->rw;
+    const float sum = (p[0] + p[1]) + p[2];
+#pragma unroll
+    for (int v = 0; v < 3; ++v) q[v] = p[v] / sum;
+#pragma unroll
+    for (int k = 0; k < 14; ++k) out[k] = (q[0] * r[0]->a[k] + q[1] * r[1]->a[k]) + q[2] * r[2]->a[k];
+    material = a.draws[PBR_BOUNDS((int64_t)s.draw, (int64_t)a.n_draws, kBoundsRaster)].material;
+    return n;
+}
+
+}  // namespace raster
+
+// The fragments stage, on the resolve's tile: 256 threads over 64 x 8 pixels, a pixel pair per lane, 8-byte plane
+// stores when VEC. slot_pixels of slots 1 .. 3: per wave and slot one ballot per pixel of the pair and one atomic.
+template <bool VEC>
+__global__ __launch_bounds__(256) void raster_fragments_msaa_kernel(const MsaaArgs m) {
+    using namespace raster;
+    const RasterArgs& a = m.r;
+    const int band_h = a.row_end - a.row_begin;
+    const int x = (int)blockIdx.x * 64 + (int)(threadIdx.x & 31u) * 2;
+    const int yb = (int)blockIdx.y * 8 + (int)(threadIdx.x >> 5);  // row of the band
+    const bool in0 = yb < band_h && x < a.width, in1 = yb < band_h && x + 1 < a.width;
+    float v0[14], v1[14], z0 = 1.0f, z1 = 1.0f;
+    uint32_t m0 = 0xFFFFu, m1 = 0xFFFFu, o0 = 0u, o1 = 0u;
+    int n0 = 0, n1 = 0;
+    if (in0) n0 = fragments_pixel(m, x, a.row_begin + yb, v0, m0, z0, o0);
+    if (in1) n1 = fragments_pixel(m, x + 1, a.row_begin + yb, v1, m1, z1, o1);
+    // (slot 0 exists in every pixel: the host stores the band's pixel count. A wave of one-fragment pixels -- nearly
+    // every wave -- then issues no atomic; one per wave on the same word would serialise the whole launch.)
+#pragma unroll
+    for (int k = 1; k < kSamples; ++k) {
+        const uint64_t b0 = __ballot(n0 > k), b1 = __ballot(n1 > k);
+        if ((threadIdx.x & 63u) == 0u && (b0 | b1) != 0ull)
+            atomicAdd(a.counters + kRasterSlotPixels + k, (unsigned long long)(__popcll(b0) + __popcll(b1)));
+    }
+    const int64_t oi = (int64_t)yb * a.stride + x;
+    if (VEC && in1) {
+        const int64_t i = PBR_BOUNDS_PIXEL(oi, a.width, band_h, a.stride, 2, kBoundsOutput);
+#pragma unroll
+        for (int k = 0; k < 14; ++k) *reinterpret_cast<float2*>(a.plane[k] + i) = make_float2(v0[k], v1[k]);
+        *reinterpret_cast<uint32_t*>(a.material + i) = m0 | (m1 << 16);
+        if (a.depth) *reinterpret_cast<float2*>(a.depth + i) = make_float2(z0, z1);
+    } else {
+        if (in0) {
+            const int64_t i = PBR_BOUNDS_PIXEL(oi, a.width, band_h, a.stride, 1, kBoundsOutput);
+#pragma unroll
+            for (int k = 0; k < 14; ++k) a.plane[k][i] = v0[k];
+            a.material[i] = (uint16_t)m0;
+            if (a.depth) a.depth[i] = z0;
+        }
+        if (in1) {
+            const int64_t i = PBR_BOUNDS_PIXEL(oi + 1, a.width, band_h, a.stride, 1, kBoundsOutput);
+#pragma unroll
+            for (int k = 0; k < 14; ++k) a.plane[k][i] = v1[k];
+            a.material[i] = (uint16_t)m1;
+            if (a.depth) a.depth[i] = z1;
+        }
+    }
+    if (m.owner != nullptr) {
+        const int64_t wi = (int64_t)yb * m.owner_stride + x;
+        if (in0) m.owner[PBR_BOUNDS_PIXEL(wi, a.width, band_h, m.owner_stride, 1, kBoundsOutput)] = (uint8_t)o0;
+        if (in1) m.owner[PBR_BOUNDS_PIXEL(wi + 1, a.width, band_h, m.owner_stride, 1, kBoundsOutput)] = (uint8_t)o1;
+    }
+}
+
+hipError_t launch_msaa_setup(const MsaaArgs& m, hipStream_t stream) {
+    if (m.r.n_tris == 0u) return hipSuccess;
+    const dim3 grid((uint32_t)(((uint64_t)m.r.n_tris + 255u) / 256u));
+    hipLaunchKernelGGL(raster_setup_msaa_kernel, grid, dim3(256), 0, stream, m);
+    return hipGetLastError();
+}
+
+hipError_t launch_msaa_large(const MsaaArgs& m, hipStream_t stream) {
+    if (m.r.n_tris == 0u) return hipSuccess;
+    const uint32_t gx = m.r.n_tris < (uint32_t)raster::kLargeGridX ? m.r.n_tris : (uint32_t)raster::kLargeGridX;
+    hipLaunchKernelGGL(raster_large_msaa_kernel, dim3(gx, raster::kLargeSlabs), dim3(256), 0, stream, m);
+    return hipGetLastError();
+}
+
+hipError_t launch_msaa_fragments(const MsaaArgs& m, hipStream_t stream) {
+    const int band_h = m.r.row_end - m.r.row_begin;
+    if (m.r.width <= 0 || band_h <= 0) return hipSuccess;
+    const dim3 grid((m.r.width + 63) / 64, (band_h + 7) / 8);
+    if (m.r.vec)
+        hipLaunchKernelGGL((raster_fragments_msaa_kernel<true>), grid, dim3(256), 0, stream, m);
+    else
+        hipLaunchKernelGGL((raster_fragments_msaa_kernel<false>), grid, dim3(256), 0, stream, m);
     return hipGetLastError();
 }
 

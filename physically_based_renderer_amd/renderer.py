@@ -503,6 +503,25 @@ class ShadingContext:
     def _rasterize(self, draws, view, flags, out, stream, layer=None) -> Attributes:
         """The three rasterising entry points behind one target set-up; ``layer``: a filled ``N.RasterLayer``."""
         v = view.to_c()
+        attrs, depth, t = self._raster_targets(view, v, out)
+        meshes = getattr(self, "meshes", ())
+        c_draws = (N.DrawDesc * max(len(draws), 1))(*[d.to_c(meshes) for d in draws])
+        if layer is not None:
+            N.check(self.lib.pbr_rasterize_layer(self._h, c_draws, len(draws), ctypes.byref(v), ctypes.byref(t),
+                                                 int(flags), ctypes.byref(layer),
+                                                 ctypes.c_void_p(_stream_handle(stream))), "pbr_rasterize_layer", self._h)
+        elif flags is None:
+            N.check(self.lib.pbr_rasterize(self._h, c_draws, len(draws), ctypes.byref(v), ctypes.byref(t),
+                                           ctypes.c_void_p(_stream_handle(stream))), "pbr_rasterize", self._h)
+        else:
+            N.check(self.lib.pbr_rasterize_flags(self._h, c_draws, len(draws), ctypes.byref(v), ctypes.byref(t),
+                                                 int(flags), ctypes.c_void_p(_stream_handle(stream))),
+                    "pbr_rasterize_flags", self._h)
+        attrs.depth = depth
+        return attrs
+
+    def _raster_targets(self, view, v, out):
+        """``out`` of a rasterising call as ``(Attributes, depth, pbr_raster_targets)``; ``v``: ``view.to_c()``."""
         rows = v.row_end - v.row_begin
         dev = torch.device("cuda", self.device)
         if out is None:
@@ -525,21 +544,7 @@ class ShadingContext:
         t.material = attrs.material.data_ptr()
         t.depth = None if depth is None else depth.data_ptr()
         t.row_stride = int(attrs.row_stride)
-        meshes = getattr(self, "meshes", ())
-        c_draws = (N.DrawDesc * max(len(draws), 1))(*[d.to_c(meshes) for d in draws])
-        if layer is not None:
-            N.check(self.lib.pbr_rasterize_layer(self._h, c_draws, len(draws), ctypes.byref(v), ctypes.byref(t),
-                                                 int(flags), ctypes.byref(layer),
-                                                 ctypes.c_void_p(_stream_handle(stream))), "pbr_rasterize_layer", self._h)
-        elif flags is None:
-            N.check(self.lib.pbr_rasterize(self._h, c_draws, len(draws), ctypes.byref(v), ctypes.byref(t),
-                                           ctypes.c_void_p(_stream_handle(stream))), "pbr_rasterize", self._h)
-        else:
-            N.check(self.lib.pbr_rasterize_flags(self._h, c_draws, len(draws), ctypes.byref(v), ctypes.byref(t),
-                                                 int(flags), ctypes.c_void_p(_stream_handle(stream))),
-                    "pbr_rasterize_flags", self._h)
-        attrs.depth = depth
-        return attrs
+        return attrs, depth, t
 
     def raster_stats(self, stream=None) -> dict:
         """pbr_last_raster_stats of the last :meth:`rasterize` on ``stream`` (synchronises it): triangles,
@@ -690,6 +695,165 @@ class ShadingContext:
             self.shade(gb, shaded, stream=stream)
             self.blend_layer(shaded, gb.opacity, coverage, frame, width=view.width, height=rows, stream=stream)
         return int(max_layers), False
+
+    def msaa_rasterize(self, draws: Sequence[Draw], view: View, flags: int = 0, surface: Optional[torch.Tensor] = None,
+                       stream=None) -> torch.Tensor:
+        """Vertex stage, setup and coverage at four samples per pixel (pbr_msaa_rasterize),
+        asynchronously. ``surface``: a (4, rows, row_stride) int64 tensor on the device holding the view's band,
+        sample-major; default: a fresh one with row_stride = width. Every word is set to all ones, then lowered to
+        ``(bits(z) << 32) | triangle ordinal`` of the fragment the sample shows. Returns the surface. ``flags`` must be
+        0 (PBR_RASTER_CLIP_NEAR and PBR_RASTER_ALPHA_TEST raise ``PbrError(PBR_ERR_UNSUPPORTED)``)."""
+        v = view.to_c()
+        if surface is None:
+            surface = torch.empty((4, max(v.row_end - v.row_begin, 0), view.width), dtype=torch.int64,
+                                  device=torch.device("cuda", self.device))
+        sf = self._msaa_surface(surface, v)
+        meshes = getattr(self, "meshes", ())
+        c_draws = (N.DrawDesc * max(len(draws), 1))(*[d.to_c(meshes) for d in draws])
+        N.check(self.lib.pbr_msaa_rasterize(self._h, c_draws, len(draws), ctypes.byref(v), int(flags), ctypes.byref(sf),
+                                            ctypes.c_void_p(_stream_handle(stream))), "pbr_msaa_rasterize", self._h)
+        return surface
+
+    def _msaa_surface(self, surface: torch.Tensor, v) -> N.MsaaSurface:
+        self._check_device(surface)
+        rows = max(v.row_end - v.row_begin, 0)
+        if (surface.dtype != torch.int64 or surface.dim() != 3 or surface.shape[0] != 4 or surface.shape[1] != rows or
+                surface.shape[2] < v.width or surface.stride(2) != 1 or surface.stride(0) != rows * surface.stride(1)):
+            raise ValueError("surface must be a (4, rows, >= width) int64 tensor whose planes follow one another")
+        sf = N.MsaaSurface()
+        sf.visibility, sf.row_stride = surface.data_ptr(), surface.stride(1)
+        return sf
+
+    def msaa_fragments(self, draws: Sequence[Draw], view: View, surface: torch.Tensor, slot: int, flags: int = 0,
+                       out=None, owner: Optional[torch.Tensor] = None, stream=None):
+        """Slot ``slot`` (0 .. 3) of every pixel out of ``surface`` (pbr_msaa_fragments): the fragment's attributes at
+        the pixel centre, its material and depth; the background planes and PBR_MATERIAL_NONE where the pixel has no
+        such slot or the fragment is the background. ``draws`` and ``view`` must be those of :meth:`msaa_rasterize`.
+        ``out`` as for :meth:`rasterize`; ``owner``: a (rows, >= width) uint8 plane that receives the owner byte
+        (the same for every slot), default a fresh one; pass ``False`` to write none. Returns ``(Attributes, owner)``
+        with the depth plane as ``.depth``."""
+        v = view.to_c()
+        sf = self._msaa_surface(surface, v)
+        attrs, depth, t = self._raster_targets(view, v, out)
+        rows = max(v.row_end - v.row_begin, 0)
+        if owner is None:
+            owner = torch.empty((rows, view.width), dtype=torch.uint8, device=torch.device("cuda", self.device))
+        elif owner is False:
+            owner = None
+        if owner is not None:
+            self._check_device(owner)
+            if (owner.dtype != torch.uint8 or owner.dim() != 2 or owner.stride(1) != 1 or owner.shape[0] < rows or
+                    owner.shape[1] < view.width):
+                raise ValueError("owner must be a (rows, >= width) uint8 plane with contiguous rows")
+        meshes = getattr(self, "meshes", ())
+        c_draws = (N.DrawDesc * max(len(draws), 1))(*[d.to_c(meshes) for d in draws])
+        N.check(self.lib.pbr_msaa_fragments(self._h, c_draws, len(draws), ctypes.byref(v), int(flags), ctypes.byref(sf),
+                                            int(slot), ctypes.byref(t),
+                                            None if owner is None else ctypes.c_void_p(owner.data_ptr()),
+                                            0 if owner is None else owner.stride(0),
+                                            ctypes.c_void_p(_stream_handle(stream))), "pbr_msaa_fragments", self._h)
+        attrs.depth = depth
+        return attrs, owner
+
+    def msaa_stats(self, stream=None) -> dict:
+        """pbr_last_msaa_stats of the last :meth:`msaa_fragments` on ``stream`` (synchronises it): ``slot_pixels``, a
+        list of the band's pixels in which slot 0 .. 3 exists; zeros after any other rasterising call."""
+        st = N.MsaaStats()
+        N.check(self.lib.pbr_last_msaa_stats(self._h, ctypes.byref(st), ctypes.c_void_p(_stream_handle(stream))),
+                "pbr_last_msaa_stats", self._h)
+        return {"slot_pixels": [int(x) for x in st.slot_pixels]}
+
+    def msaa_resolve(self, slots: Sequence[Optional[torch.Tensor]], owner: torch.Tensor,
+                     out: Optional[torch.Tensor] = None, fmt: int = N.PBR_OUTPUT_RGBA32F, n_slots: Optional[int] = None,
+                     width: Optional[int] = None, height: Optional[int] = None, stream=None) -> torch.Tensor:
+        """The multisample resolve (pbr_msaa_resolve), asynchronously: per pixel and channel
+        ``((c0 + c1) + (c2 + c3)) * 0.25`` with ``c_s`` the pixel of the slot frame that owns sample s by ``owner``
+        (0 where that slot is >= ``n_slots``). ``slots``: up to four (H, >= W, 4) float32 frames with one row stride
+        (entries past ``n_slots``, default ``len(slots)``, may be None); ``out``: (H, >= W, 4) float32 (RGBA32F) or
+        uint8 (RGBA8_UNORM: every sample goes through the UNORM8 encoding first), default a fresh frame of ``fmt``."""
+        slots = list(slots)
+        n = len(slots) if n_slots is None else int(n_slots)
+        self._check_device(owner, out, *slots)
+        live = [s for s in slots[:max(n, 0)] if s is not None]
+        for s in live:
+            if s.dtype != torch.float32 or s.dim() != 3 or s.shape[2] != 4 or s.stride(2) != 1 or s.stride(1) != 4:
+                raise ValueError("a slot frame must be (H, W, 4) float32 with contiguous pixels")
+        if not live or any(s.stride(0) != live[0].stride(0) for s in live):
+            raise ValueError("the slot frames need one row stride, and slot 0 must be there")
+        if owner.dtype != torch.uint8 or owner.dim() != 2 or owner.stride(1) != 1:
+            raise ValueError("owner must be a (H, W) uint8 plane with contiguous rows")
+        h = min(live[0].shape[0], owner.shape[0]) if height is None else int(height)
+        w = min(live[0].shape[1], owner.shape[1]) if width is None else int(width)
+        if out is None:
+            out = torch.empty((h, w, 4), dtype=torch.uint8 if fmt == N.PBR_OUTPUT_RGBA8_UNORM else torch.float32,
+                              device=owner.device)
+        if out.dtype == torch.uint8:
+            fmt = N.PBR_OUTPUT_RGBA8_UNORM
+        elif out.dtype == torch.float32:
+            fmt = N.PBR_OUTPUT_RGBA32F
+        else:
+            raise ValueError("out must be float32 (RGBA32F) or uint8 (RGBA8_UNORM)")
+        if out.dim() != 3 or out.shape[2] != 4 or out.stride(2) != 1 or out.stride(1) != 4:
+            raise ValueError("out must be (H, W, 4) with contiguous pixels")
+        for t in live + [owner, out]:
+            if t.shape[0] < h or t.shape[1] < w:
+                raise ValueError("a plane is smaller than the resolved rectangle")
+        src = N.MsaaResolveSource()
+        src.slots[:] = [None if s is None else s.data_ptr() for s in (slots + [None] * 4)[:4]]
+        src.slot_row_stride = live[0].stride(0) // 4
+        src.n_slots = n
+        src.owner, src.owner_row_stride = owner.data_ptr(), owner.stride(0)
+        f = N.FrameDesc()
+        f.out = out.data_ptr()
+        f.out_row_stride = out.stride(0) // 4
+        f.format = int(fmt)
+        N.check(self.lib.pbr_msaa_resolve(self._h, ctypes.byref(src), ctypes.byref(f), w, h,
+                                          ctypes.c_void_p(_stream_handle(stream))), "pbr_msaa_resolve", self._h)
+        return out
+
+    def draw_msaa(self, draws: Sequence[Draw], view: View, *, filter: int = N.PBR_FILTER_POINT,
+                  mip_lod_bias: Optional[float] = None, max_anisotropy: Optional[int] = None,
+                  fmt: int = N.PBR_OUTPUT_RGBA32F, out: Optional[torch.Tensor] = None, stream=None):
+        """``draws`` under ``view`` with four samples per pixel (the reference's m_4xMsaaState): :meth:`msaa_rasterize`,
+        then for every slot some pixel has :meth:`msaa_fragments` -> :meth:`resolve` (``filter``; ``mip_lod_bias`` /
+        ``max_anisotropy`` choose :meth:`resolve_mip` / :meth:`resolve_aniso` as in :meth:`draw_transparent`, with its
+        rule for the band) -> :meth:`shade_frame` with the slot's coverage plane, so background fragments get the sky,
+        into RGBA32F; then :meth:`msaa_resolve` into ``out`` (default: a fresh frame of ``fmt``). The pass of
+        :meth:`set_pass` shades every slot (set ``PBR_FLAG_F0_PLANE``); every slot shades the whole band. Returns
+        ``(frame, slots)`` with ``slots`` the number of slots shaded. Synchronises ``stream`` once, to read the slot
+        counters."""
+        v = view.to_c()
+        rows = max(v.row_end - v.row_begin, 0)
+        dev = torch.device("cuda", self.device)
+        if rows == 0 or view.width == 0:  # an empty band: nothing to draw
+            dtype = torch.uint8 if fmt == N.PBR_OUTPUT_RGBA8_UNORM else torch.float32
+            return (torch.empty((rows, view.width, 4), dtype=dtype, device=dev) if out is None else out), 0
+        surface = self.msaa_rasterize(draws, view, stream=stream)
+        attrs = Attributes(torch.empty((N.NUM_ATTRIBUTE_PLANES, rows, view.width), dtype=torch.float32, device=dev),
+                           torch.empty((rows, view.width), dtype=torch.int16, device=dev))
+        gb = GBuffer(torch.empty((N.NUM_PLANES, rows, view.width), dtype=torch.float32, device=dev),
+                     opacity=torch.empty((rows, view.width), dtype=torch.float32, device=dev))
+        coverage = torch.empty((rows, view.width), dtype=torch.uint8, device=dev)
+        owner, n_slots, shaded = None, 1, []
+        k = 0
+        while k < n_slots:
+            _, written = self.msaa_fragments(draws, view, surface, k, out=attrs, owner=None if k == 0 else False,
+                                             stream=stream)
+            if k == 0:
+                owner = written
+                pixels = self.msaa_stats(stream)["slot_pixels"]
+                n_slots = max(1, sum(1 for p in pixels if p > 0))
+            if max_anisotropy is not None:
+                self.resolve_aniso(attrs, max_anisotropy, 0.0 if mip_lod_bias is None else mip_lod_bias,
+                                   out=(gb, coverage), stream=stream)
+            elif mip_lod_bias is None:
+                self.resolve(attrs, filter, out=(gb, coverage), stream=stream)
+            else:
+                self.resolve_mip(attrs, mip_lod_bias, out=(gb, coverage), stream=stream)
+            shaded.append(self.shade_frame(gb, coverage=coverage, fmt=N.PBR_OUTPUT_RGBA32F, stream=stream))
+            k += 1
+        frame = self.msaa_resolve(shaded, owner, out=out, fmt=fmt, width=view.width, height=rows, stream=stream)
+        return frame, n_slots
 
     def _check_device(self, *tensors) -> None:
         """Every tensor handed to the kernel must live on this context's device: a foreign pointer would be
