@@ -1,8 +1,10 @@
 // frontend_kernels.hip -- gfx950 kernels of the front end, which turns meshes and materials into the G-buffer the
 // shading kernels read: the rasteriser (raster.h; pbr_rasterize) and the material resolve (material_resolve.h;
-// pbr_resolve_materials); and the blend of a shaded transparent layer over the frame (blend_layer.h; pbr_blend_layer). A unit of its own, so a front-end change never recompiles the shading kernels. The Makefile
-// gives it the flags these kernels were first built and measured under: the canonical fp32 flags and the max-ILP
-// machine scheduler.
+// pbr_resolve_materials); and the blend of a shaded transparent layer over the frame (blend_layer.h; pbr_blend_layer).
+// raster.h states each rule of DESIGN.md §12 once where that leaves every kernel of this unit as it was (its header
+// lists what stays apart and the comparison that decided it). A unit of its own, so a front-end change never
+// recompiles the shading kernels. The Makefile gives it the flags these kernels were first built and measured
+// under: the canonical fp32 flags and the max-ILP machine scheduler.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>

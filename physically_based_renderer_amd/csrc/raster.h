@@ -1,56 +1,77 @@
 // raster.h -- VS (Default.hlsl:22-45) and the rasteriser behind DrawIndexedInstanced (PBRApp.cpp:1133) on the device:
 // indexed triangle lists in, the 14 planes of a pbr_attributes_soa, the material plane and the depth plane out
-// (pbr_rasterize, include/pbr/pbr_shade.h; DESIGN.md §12 fixes every operation). A source of frontend_kernels.hip, which
-// is compiled with the canonical fp32 flags: no contraction, correctly rounded / and sqrt.
+// (pbr_rasterize and its flagged, layer and multisampled forms, include/pbr/pbr_shade.h; DESIGN.md §12 fixes every
+// operation). A source of frontend_kernels.hip, which is compiled with the canonical fp32 flags: no contraction,
+// correctly rounded / and sqrt.
 //
-// Four launches, stream-ordered, none waiting on another workgroup:
-//   1. raster_vertex_kernel: one lane per (draw, vertex): VS, the perspective division, the viewport and the snap
-//      to 1/256 pixel into a RasterVertex record.
-//   2. raster_setup_kernel: one lane per triangle: skip tests, the signed area in int64, culling, the bounding box
-//      clipped to the band. A triangle whose clipped box holds at most kSmallPixels pixels is rasterised by its lane;
-//      the others are appended to the large list through one atomic per wave.
-//   3. raster_large_kernel: a workgroup per large triangle (grid-stride over the list) and kLargeSlabs workgroups
-//      across its 64 x 4 pixel blocks; a block every pixel of which some edge function rejects (its maximum over the
-//      block's corners is negative) is skipped. So one triangle over the whole frame is spread over kLargeSlabs
-//      workgroups, and 10^5 sub-pixel triangles never reach this kernel.
-//   4. raster_resolve_kernel: per pixel (the material resolve's 64 x 8 tile, a pixel pair per lane): the visibility
-//      word names the winning triangle; its records are fetched again, the edge functions and barycentrics
-//      recomputed with the operations of the coverage test, the attributes interpolated and stored.
-// Visibility is one 64-bit word per band pixel, (bits(z) << 32) | triangle ordinal, cleared to all ones and lowered
-// by a global 64-bit atomicMin: the smallest key wins whatever the execution order.
+// Stages: four launches, stream-ordered, none waiting on another workgroup.
+//   1. Vertex (raster_vertex_kernel): one lane per (draw, vertex): VS, the perspective division, the viewport and the
+//      snap to 1/256 pixel into a RasterVertex record.
+//   2. Setup (raster_setup_kernel; raster_setup_clip_kernel; raster_setup_msaa_kernel): one lane per triangle:
+//      tri_setup (the skip tests; tri_area: the signed area in int64 and culling), tri_box clipped to the band. A
+//      triangle whose box holds at most kSmallPixels pixels is rasterised by its lane; the others go to the large
+//      list through one atomic per wave (append_large).
+//   3. Large (raster_large_kernel; raster_large_msaa_kernel): a workgroup per listed triangle (grid-stride over the
+//      list) and kLargeSlabs workgroups across its 64 x 4 pixel blocks; a block every point of which some edge
+//      function rejects (its maximum over the block's corners is negative) is skipped. So one triangle over the
+//      whole frame is spread over kLargeSlabs workgroups, and 10^5 sub-pixel triangles never reach this kernel.
+//   4. Resolve (raster_resolve_kernel; raster_fragments_msaa_kernel): per pixel, on the material resolve's 64 x 8 tile,
+//      a pixel pair per lane: the visibility word names the winning triangle; its records are fetched again, the edge
+//      functions and barycentrics recomputed with the operations of the coverage test, the attributes interpolated
+//      (perspective_weights, interpolate) and stored.
+// Stages 2 and 3 meet in raster_point<Mode> (steps 5-7 for a pixel centre: edge_at_centre, covered, barycentrics,
+// interpolate_z, the depth range, the mode's test, the key), which returns one result word (kFragment, kFragTested,
+// kFragDiscarded, kFragUpdate) that one Counts sums; the setup lanes reach it through raster_small<Mode>. Visibility is
+// one 64-bit word per band pixel, cleared to all ones and lowered by a global 64-bit atomicMin: the smallest key wins
+// whatever the execution order.
 //
-// Near-plane clipping (pbr_rasterize_flags with PBR_RASTER_CLIP_NEAR) is a second instantiation
-// of each kernel (template parameter CLIP; raster_setup_clip_kernel for the setup, whose piece loop has another shape),
-// launched for a flagged call only; the CLIP = false instantiations are the kernels of pbr_rasterize, instruction for
-// instruction. The vertex kernel also stores PosH (16 bytes per record) and marks the vertices with PosH.z not >= 0
-// as outside. A triangle with 1 or 2 inside vertices becomes 1 or 2 pieces whose new vertices -- the crossings of its
-// edges with z = 0, each computed from the inside vertex to the outside one -- are never stored: setup, the
-// large-triangle kernel and the resolve rebuild a piece from the triangle's ordinal and the piece's number with the
-// same operations (piece_setup), so the resolve reproduces the key's z bits as it does for an unclipped triangle. A
-// large-list entry carries the piece's number in the top bit of its block count (a block count is below 2^23: frames
-// are at most 32,768 on a side).
+// Variants: each is a template parameter of the kernels it reaches, selected with `if constexpr`, and the launch
+// functions turn the call's runtime flags into them (with_bool, with_mode). An unflagged pbr_rasterize launches the
+// all-false instantiations, which carry nothing of the others. The setup and large kernels' (ALPHA, PEEL) is the
+// Mode of their points (mode_of): Plain, Alpha or Peel.
+//   CLIP   (PBR_RASTER_CLIP_NEAR; step 2a; vertex, setup, large, resolve) the vertex stage also stores PosH (16 bytes
+//          per record) and marks the vertices with PosH.z not >= 0 as outside. A triangle with 1 or 2 inside vertices
+//          becomes 1 or 2 pieces whose new vertices -- the crossings of its edges with z = 0, each computed from the
+//          inside vertex to the outside one and taken through project() -- are never stored: setup, large and the
+//          resolve rebuild a piece from the triangle's ordinal and the piece's number with the same operations
+//          (piece_setup), so the resolve reproduces the key's z bits as it does for an unclipped triangle. A large-list
+//          entry carries the piece's number in the top bit of its block count (a block count is below 2^23: frames
+//          are at most 32,768 on a side).
+//   ALPHA  (PBR_RASTER_ALPHA_TEST and some draw with a PBR_MAT_ALPHA_TEST material; step 6a; Default.hlsl:111-113;
+//          setup, large; Mode::Alpha) a fragment of a tested draw interpolates its TexCoord with the resolve's
+//          operations, fetches the material resolve's point-wrap tap of the opacity texture and, with
+//          opacity - 0.1 < 0, issues no visibility update. The winner is still the key's triangle.
+//   PEEL   (pbr_rasterize_layer; step 7a; RenderLayer::Transparent, PBRApp.cpp:313-316: depth LESS with writes on,
+//          blending; setup, large, resolve; Mode::Peel; never with ALPHA) a fragment is eligible iff its
+//          ordinal is at least the pixel's floor and its z is below the incoming depth; the key is
+//          (ordinal << 32) | bits(z) instead of (bits(z) << 32) | ordinal, so the earliest eligible fragment in
+//          submission order wins -- the next one the D3D depth test would accept. The resolve writes that fragment's
+//          attributes, its z as the new depth and its ordinal + 1 as the next floor; a pixel without one keeps the
+//          incoming depth and gets the floor 0xFFFFFFFF.
+//   VEC    (resolve, fragments) every plane is 8-byte aligned with an even stride: a lane stores its pair at once.
+//   Four samples per pixel (pbr_msaa_rasterize, pbr_msaa_fragments; step 7b; the three *_msaa kernels, whose MsaaArgs
+//          hold the caller's surface; raster_pixel_samples) steps 5-7 at the four sample points of a pixel into one
+//          word per (sample, pixel), sample-major; boxes and the block rejection reach kSampleReach further. The
+//          fragments stage takes the resolve's place: the samples of a pixel with the same triangle are one fragment,
+//          numbered as slots by their lowest sample; a slot's attributes are step 8 at the pixel centre, covered
+//          or not.
 //
-// The alpha test (pbr_rasterize_flags with PBR_RASTER_ALPHA_TEST; RenderLayer::AlphaTested,
-// Default.hlsl:111-113) is a further instantiation (template parameter ALPHA) of the kernels that run the coverage test
-// -- the two setup kernels and the large-triangle kernel -- launched only when some draw of a flagged call has a
-// material with PBR_MAT_ALPHA_TEST; the ALPHA = false instantiations are the kernels of an unflagged call, instruction
-// for instruction. A fragment of a tested draw interpolates its TexCoord with the resolve's operations, fetches the
-// material resolve's point-wrap tap of the opacity texture and, with opacity - 0.1 < 0, issues no visibility update.
-// The vertex and resolve kernels do not change: the winner is still the key's triangle.
-//
-// A layer of the transparent pass (pbr_rasterize_layer; RenderLayer::Transparent,
-// PBRApp.cpp:313-316: depth LESS with writes on, blending) is a further instantiation (template parameter PEEL) of the
-// setup kernels, the large-triangle kernel and the resolve, launched by a layer call only and never with ALPHA; the
-// PEEL = false instantiations are the kernels of the other calls, instruction for instruction. A fragment is eligible
-// iff its ordinal is at least the pixel's floor and its z is below the incoming depth; the visibility word is
-// (ordinal << 32) | bits(z), so the atomicMin keeps the earliest eligible fragment in submission order -- the next
-// fragment the D3D depth test would accept. The resolve writes that fragment's attributes, its z as the new depth and
-// its ordinal + 1 as the next floor; a pixel without one keeps the incoming depth and gets the floor 0xFFFFFFFF.
-//
-// Four samples per pixel (pbr_msaa_rasterize, pbr_msaa_fragments) are kernels of their own at
-// the end of this file -- raster_setup_msaa_kernel, raster_large_msaa_kernel, raster_fragments_msaa_kernel -- launched
-// by the multisampled calls only; the kernels of every other call are what they were, instruction for instruction.
+// What is still written more than once, and why: a helper that a kernel calls is simplified on its own before it is
+// inlined, and the schedule of the kernel follows. Every sharing below was compiled and compared with
+// tools/isa_compare.py (profiles/raster_once/); it stays apart where it changed a kernel, because the kernels of an
+// unflagged pbr_rasterize must stay instruction for instruction what every earlier measurement timed, and the changed
+// kernels of the other calls have not been timed on a device.
+//   - steps 2-3 in raster_vertex_kernel and project() (vertex_calls_project.txt: 304 -> 323 instructions);
+//   - step 4's end in piece_setup and tri_area (piece_setup_calls_tri_area.txt: the ten CLIP kernels change);
+//   - steps 5-7 in raster_pixel_samples and raster_point (samples_in_point_routine.txt: both *_msaa coverage kernels
+//     change); the unflagged setup kernel's small-box loop (small_loop_as_function.txt);
+//   - the setup and large flows and the tile's pair store of the *_msaa kernels (kernel_body_as_function.txt,
+//     pair_store_as_function.txt: a kernel body moved into a function, verbatim, changes all of them);
+//   - l_i rw_i before perspective_weights (weights_with_products.txt: the helper that also forms the products changes
+//     the resolve kernels by 0 or 1 instruction).
 #pragma once
+
+#include <type_traits>
 
 #include "pbr_device_math.h"
 #include "frontend_kernels.h"
@@ -64,6 +85,12 @@ constexpr int kSmallPixels = 64;   // clipped bounding boxes up to this many pix
 constexpr int kLargeSlabs = 32;    // workgroups across one large triangle's blocks
 constexpr int kLargeGridX = 1024;  // workgroups (x) striding over the large list
 constexpr int kBlockW = 64, kBlockH = 4;
+constexpr int kSamples = 4;
+constexpr int kSampleReach = 96;  // no sample is further from its pixel's centre, in subpixels, along either axis
+
+// What a point's fragment has to pass and which key it writes (the header comment); the 1x kernels' (ALPHA, PEEL).
+enum class Mode { Plain, Alpha, Peel };
+constexpr Mode mode_of(bool alpha, bool peel) { return alpha ? Mode::Alpha : (peel ? Mode::Peel : Mode::Plain); }
 
 // mul(v, M)[j] for a row vector: the 4-wide dot ((x + y) + z) + w, M row-major.
 __device__ __forceinline__ float mul4(float x, float y, float z, float w, const float* m, int j) {
@@ -89,7 +116,7 @@ __device__ __forceinline__ int find_draw(const uint32_t* prefix, int n, uint32_t
 
 // Steps 2-3 on a piece's new vertex (piece_setup): the near test on w, the three divisions, the viewport, the snap to
 // 1/256 pixel and the guard band, operation for operation what raster_vertex_kernel does to a submitted vertex (which
-// keeps them written out: calling this from it changes the unflagged kernel's register allocation and schedule).
+// keeps them written out: profiles/raster_once/vertex_calls_project.txt).
 struct Projected {
     int X, Y;
     float z, rw;
@@ -123,6 +150,26 @@ struct Tri {
     int draw;
 };
 
+// Step 4's end on the snapped positions of s: the signed area in int64, the zero-area and cull tests and, for a back
+// face drawn under cull none, the exchange of vertices 1 and 2 in s.
+__device__ __forceinline__ TriStatus tri_area(const RasterDraw& dr, Tri& s) {
+    long long A = (long long)(s.X[1] - s.X[0]) * (long long)(s.Y[2] - s.Y[0]) -
+                  (long long)(s.X[2] - s.X[0]) * (long long)(s.Y[1] - s.Y[0]);
+    if (A == 0) return kTriZeroArea;
+    if (A < 0) {
+        if (dr.cull == 0u) return kTriCulled;
+        const uint32_t r1 = s.rec[1];
+        s.rec[1] = s.rec[2];
+        s.rec[2] = r1;
+        const int x1 = s.X[1], y1 = s.Y[1];
+        s.X[1] = s.X[2], s.Y[1] = s.Y[2];
+        s.X[2] = x1, s.Y[2] = y1;
+        A = -A;
+    }
+    s.A = A;
+    return kTriDraw;
+}
+
 // CLIP: `outside` receives the mask of the vertices (in index order) marked kVertexOutside; with none of them the
 // triangle is set up as without CLIP, with all three it is kTriNear (step 2a: n = 0), otherwise kTriClipped with
 // s.rec in index order and s.draw set (piece_setup goes on from there).
@@ -152,35 +199,24 @@ __device__ __forceinline__ TriStatus tri_setup(const RasterArgs& a, uint32_t t, 
     }
     if (flags & kVertexNear) return kTriNear;
     if (flags & kVertexGuard) return kTriGuard;
-    long long A = (long long)(s.X[1] - s.X[0]) * (long long)(s.Y[2] - s.Y[0]) -
-                  (long long)(s.X[2] - s.X[0]) * (long long)(s.Y[1] - s.Y[0]);
-    if (A == 0) return kTriZeroArea;
-    if (A < 0) {
-        if (dr.cull == 0u) return kTriCulled;
-        const uint32_t r1 = s.rec[1];
-        s.rec[1] = s.rec[2];
-        s.rec[2] = r1;
-        const int x1 = s.X[1], y1 = s.Y[1];
-        s.X[1] = s.X[2], s.Y[1] = s.Y[2];
-        s.X[2] = x1, s.Y[2] = y1;
-        A = -A;
-    }
-    s.A = A;
-    return kTriDraw;
+    return tri_area(dr, s);
 }
 
-// The pixels whose centres can lie inside the triangle, clipped to the band; false when there are none.
+// The pixels that have a point within `reach` subpixels of their centre, along both axes, inside the triangle's
+// bounding box, clipped to the band; false when there are none. Reach 0: the pixels whose centres can lie inside the triangle.
+// Reach kSampleReach: those with a sample that can; conservative: every point that near counts, sample or not.
 struct Box {
     int x0, x1, y0, y1;  // inclusive
 };
-__device__ __forceinline__ bool tri_box(const RasterArgs& a, const Tri& s, Box& b) {
+__device__ __forceinline__ bool tri_box(const RasterArgs& a, const Tri& s, int reach, Box& b) {
     const int minx = min(s.X[0], min(s.X[1], s.X[2])), maxx = max(s.X[0], max(s.X[1], s.X[2]));
     const int miny = min(s.Y[0], min(s.Y[1], s.Y[2])), maxy = max(s.Y[0], max(s.Y[1], s.Y[2]));
-    // centre 256 p + 128 in [min, max]  <=>  p in [ceil((min - 128) / 256), floor((max - 128) / 256)]
-    b.x0 = max((minx - 128 + 255) >> 8, 0);
-    b.x1 = min((maxx - 128) >> 8, a.width - 1);
-    b.y0 = max((miny - 128 + 255) >> 8, a.row_begin);
-    b.y1 = min((maxy - 128) >> 8, a.row_end - 1);
+    // 256 p + 128 + reach >= min and 256 p + 128 - reach <= max
+    //   <=>  p in [ceil((min - 128 - reach) / 256), floor((max - 128 + reach) / 256)]
+    b.x0 = max((minx - (128 + reach) + 255) >> 8, 0);
+    b.x1 = min((maxx - (128 - reach)) >> 8, a.width - 1);
+    b.y0 = max((miny - (128 + reach) + 255) >> 8, a.row_begin);
+    b.y1 = min((maxy - (128 - reach)) >> 8, a.row_end - 1);
     return b.x0 <= b.x1 && b.y0 <= b.y1;
 }
 
@@ -200,10 +236,13 @@ __device__ __forceinline__ void tri_edges(const Tri& s, Edges& e) {
         e.top_left[k] = e.dy[k] < 0 || (e.dy[k] == 0 && e.dx[k] > 0);
     }
 }
-// E = (Xb - Xa)(Py - Ya) - (Yb - Ya)(Px - Xa) at the centre of pixel (x, y), exact in int64.
-__device__ __forceinline__ long long edge_at(const Edges& e, int k, int x, int y) {
-    const int px = 256 * x + 128, py = 256 * y + 128;
+// E = (Xb - Xa)(Py - Ya) - (Yb - Ya)(Px - Xa) at the point (px, py) of the subpixel grid, exact in int64; and at the
+// centre of pixel (x, y), which is (256 x + 128, 256 y + 128).
+__device__ __forceinline__ long long edge_at(const Edges& e, int k, int px, int py) {
     return (long long)e.dx[k] * (long long)(py - e.ya[k]) - (long long)e.dy[k] * (long long)(px - e.xa[k]);
+}
+__device__ __forceinline__ long long edge_at_centre(const Edges& e, int k, int x, int y) {
+    return edge_at(e, k, 256 * x + 128, 256 * y + 128);
 }
 __device__ __forceinline__ bool covered(const Edges& e, const long long E[3]) {
     bool in = true;
@@ -221,19 +260,14 @@ __device__ __forceinline__ float interpolate_z(const float l[3], const float z[3
     return ((l[0] * z[0] + l[1] * z[1]) + l[2] * z[2]) + 0.0f;
 }
 
-// Coverage, depth range and the visibility update of one pixel (steps 5-7); 1 when a fragment exists.
-__device__ __forceinline__ uint32_t raster_pixel(const RasterArgs& a, const Tri& s, const Edges& e, const float z[3],
-                                                 uint32_t prim, int x, int y) {
-    const long long E[3] = {edge_at(e, 0, x, y), edge_at(e, 1, x, y), edge_at(e, 2, x, y)};
-    if (!covered(e, E)) return 0u;
-    float l[3];
-    barycentrics(E, s.A, l);
-    const float zf = interpolate_z(l, z);
-    if (!(zf >= 0.0f && zf < 1.0f)) return 0u;  // depth clip and LESS against 1; NaN: no fragment
-    const unsigned long long key = ((unsigned long long)__float_as_uint(zf) << 32) | (unsigned long long)prim;
-    [[maybe_unused]] const int64_t n_vis = (int64_t)(a.row_end - a.row_begin) * a.width;
-    atomicMin(a.vis + PBR_BOUNDS((int64_t)(y - a.row_begin) * a.width + x, n_vis, kBoundsRaster), key);
-    return 1u;
+// Step 8's weights from p_i = l_i rw_i: q_i = p_i / ((p0 + p1) + p2); and a value interpolated with them.
+__device__ __forceinline__ void perspective_weights(const float p[3], float q[3]) {
+    const float sum = (p[0] + p[1]) + p[2];
+#pragma unroll
+    for (int v = 0; v < 3; ++v) q[v] = p[v] / sum;
+}
+__device__ __forceinline__ float interpolate(const float q[3], float a0, float a1, float a2) {
+    return (q[0] * a0 + q[1] * a1) + q[2] * a2;
 }
 
 __device__ __forceinline__ void load_z(const RasterArgs& a, const Tri& s, float z[3]) {
@@ -241,7 +275,7 @@ __device__ __forceinline__ void load_z(const RasterArgs& a, const Tri& s, float 
     for (int v = 0; v < 3; ++v) z[v] = a.records[PBR_BOUNDS((int64_t)s.rec[v], (int64_t)a.n_records, kBoundsRaster)].z;
 }
 
-// ---- Alpha test (step 6a; the ALPHA instantiations) ----
+// ---- Alpha test (step 6a; Mode::Alpha) ----
 // What the test needs of a triangle (or piece): whether its draw is tested, the opacity texture of the draw's material
 // record, and 1 / w and TexCoord of the three vertices in setup's order. Filled only for a tested draw.
 struct AlphaTri {
@@ -283,82 +317,132 @@ __device__ __forceinline__ bool alpha_discards(const RasterArgs& a, const AlphaT
     float p[3], q[3];
 #pragma unroll
     for (int v = 0; v < 3; ++v) p[v] = l[v] * al.rw[v];
-    const float sum = (p[0] + p[1]) + p[2];
-#pragma unroll
-    for (int v = 0; v < 3; ++v) q[v] = p[v] / sum;
-    const float tu = (q[0] * al.u[0] + q[1] * al.u[1]) + q[2] * al.u[2];
-    const float tv = (q[0] * al.v[0] + q[1] * al.v[1]) + q[2] * al.v[2];
+    perspective_weights(p, q);
+    const float tu = interpolate(q, al.u[0], al.u[1], al.u[2]);
+    const float tv = interpolate(q, al.v[0], al.v[1], al.v[2]);
     const float o = resolve::unorm8(resolve::tap_point(a.texels, a.n_texels, al.tex, tu, tv), 0);
     return o - 0.1f < 0.0f;
 }
 
-// raster_pixel with step 6a between the depth range and the visibility update. Bit 0: a fragment exists; bit 1: it
-// reached the test; bit 2: the test discarded it (no visibility update).
-constexpr uint32_t kFragment = 1u, kFragTested = 2u, kFragDiscarded = 4u;
-__device__ __forceinline__ uint32_t raster_pixel_alpha(const RasterArgs& a, const Tri& s, const Edges& e,
-                                                       const float z[3], const AlphaTri& al, uint32_t prim, int x,
-                                                       int y) {
-    const long long E[3] = {edge_at(e, 0, x, y), edge_at(e, 1, x, y), edge_at(e, 2, x, y)};
+// ---- One point (steps 5-7) ----
+// Sample sm of a pixel is at (256 x + 128 + sample_dx(sm), 256 y + 128 + sample_dy(sm)): (-2, -6), (6, -2), (-6, 2),
+// (2, 6) sixteenths of a pixel from the centre, D3D's standard pattern, which lies on the 1/256 grid.
+__device__ __forceinline__ int sample_dx(int s) { return s == 0 ? -32 : (s == 1 ? 96 : (s == 2 ? -96 : 32)); }
+__device__ __forceinline__ int sample_dy(int s) { return s == 0 ? -96 : (s == 1 ? -32 : (s == 2 ? 32 : 96)); }
+
+// What became of a point. kFragment: a fragment exists (covered, z in [0, 1)). Mode::Alpha: kFragTested: it reached
+// the alpha test; kFragDiscarded: the test discarded it (no visibility update). Mode::Peel: kFragUpdate: it was
+// eligible and issued a visibility update.
+constexpr uint32_t kFragment = 1u, kFragTested = 2u, kFragDiscarded = 4u, kFragUpdate = 2u;
+
+// A lane's (or workgroup's) counts of those results; a mode counts its own bits. kFragTested and kFragUpdate are the
+// same bit and share the field `bit1`: a kernel has one mode, and a call with ALPHA and PEEL together would need a bit
+// and a field of its own for the updates (the kernels' static_asserts refuse that pair today; a fourth field changes
+// the layer setup kernel: profiles/raster_once/counts_with_four_fields.txt).
+struct Counts {
+    uint32_t frags = 0, bit1 = 0, discarded = 0;
+    static_assert(kFragTested == kFragUpdate, "bit1 counts one of them: separate them before a mode has both");
+    __device__ __forceinline__ uint32_t tested() const { return bit1; }   // Mode::Alpha
+    __device__ __forceinline__ uint32_t updates() const { return bit1; }  // Mode::Peel
+    template <Mode M>
+    __device__ __forceinline__ void add(uint32_t r) {
+        if constexpr (M == Mode::Alpha) {
+            frags += r & 1u;
+            bit1 += (r >> 1) & 1u;
+            discarded += r >> 2;
+        } else if constexpr (M == Mode::Peel) {
+            frags += r & 1u;
+            bit1 += r / kFragUpdate;
+        } else {
+            frags += r;
+        }
+    }
+};
+
+// Coverage, the depth range, the mode's test and the visibility update at the centre of pixel (x, y) for triangle (or
+// piece) s with ordinal prim; the result word.
+// Mode::Alpha: step 6a, with al, between the depth range and the update.
+// Mode::Peel: the eligibility test there, and the key's halves exchanged: (ordinal << 32) | bits(z), so the smallest
+// eligible ordinal wins. A fragment is eligible iff z < depth_in (a NaN depth_in: never) and prim >= the floor.
+// depth_in and prim_in are read only after coverage and the depth range passed; both only read here (the resolve,
+// later in stream order, is what may overwrite them).
+template <Mode M>
+__device__ __forceinline__ uint32_t raster_point(const RasterArgs& a, const Tri& s, const Edges& e, const float z[3],
+                                                 const AlphaTri* al, uint32_t prim, int x, int y) {
+    const long long E[3] = {edge_at_centre(e, 0, x, y), edge_at_centre(e, 1, x, y), edge_at_centre(e, 2, x, y)};
     if (!covered(e, E)) return 0u;
     float l[3];
     barycentrics(E, s.A, l);
     const float zf = interpolate_z(l, z);
-    if (!(zf >= 0.0f && zf < 1.0f)) return 0u;
+    if (!(zf >= 0.0f && zf < 1.0f)) return 0u;  // depth clip and LESS against 1; NaN: no fragment
     uint32_t r = kFragment;
-    if (al.tested) {
-        r |= kFragTested;
-        if (alpha_discards(a, al, l)) return r | kFragDiscarded;
+    if constexpr (M == Mode::Alpha) {
+        if (al->tested) {
+            r |= kFragTested;
+            if (alpha_discards(a, *al, l)) return r | kFragDiscarded;
+        }
     }
-    const unsigned long long key = ((unsigned long long)__float_as_uint(zf) << 32) | (unsigned long long)prim;
-    [[maybe_unused]] const int64_t n_vis = (int64_t)(a.row_end - a.row_begin) * a.width;
+    [[maybe_unused]] const int band_h = a.row_end - a.row_begin;
+    if constexpr (M == Mode::Peel) {
+        const int64_t i = PBR_BOUNDS_PIXEL((int64_t)(y - a.row_begin) * a.stride + x, a.width, band_h, a.stride, 1,
+                                           kBoundsRaster);
+        if (!(zf < a.depth_in[i])) return kFragment;
+        if (a.prim_in != nullptr && prim < a.prim_in[i]) return kFragment;
+    }
+    unsigned long long key;
+    if constexpr (M == Mode::Peel)
+        key = ((unsigned long long)prim << 32) | (unsigned long long)__float_as_uint(zf);
+    else
+        key = ((unsigned long long)__float_as_uint(zf) << 32) | (unsigned long long)prim;
+    [[maybe_unused]] const int64_t n_vis = (int64_t)band_h * a.width;
     atomicMin(a.vis + PBR_BOUNDS((int64_t)(y - a.row_begin) * a.width + x, n_vis, kBoundsRaster), key);
+    if constexpr (M == Mode::Peel) return kFragment | kFragUpdate;
     return r;
 }
 
-// A lane's (or workgroup's) fragment counts: those that exist, those tested, those discarded.
-struct FragCounts {
-    uint32_t frags = 0, tested = 0, discarded = 0;
-    __device__ __forceinline__ void add(uint32_t r) {
-        frags += r & 1u;
-        tested += (r >> 1) & 1u;
-        discarded += r >> 2;
-    }
-};
-
-// ---- Layer peel (step 7a; the PEEL instantiations; pbr_rasterize_layer) ----
-// raster_pixel with the eligibility test between the depth range and the visibility update, and the key's halves
-// exchanged: (ordinal << 32) | bits(z), so the smallest eligible ordinal wins. A fragment is eligible iff
-// z < depth_in (a NaN depth_in: never) and prim >= the floor. depth_in and prim_in are read only after coverage and
-// the depth range passed; both only read here (the resolve, later in stream order, is what may overwrite them).
-// Bit 0: a fragment exists; bit 1: it issued a visibility update.
-constexpr uint32_t kFragUpdate = 2u;
-__device__ __forceinline__ uint32_t raster_pixel_peel(const RasterArgs& a, const Tri& s, const Edges& e,
-                                                      const float z[3], uint32_t prim, int x, int y) {
-    const long long E[3] = {edge_at(e, 0, x, y), edge_at(e, 1, x, y), edge_at(e, 2, x, y)};
-    if (!covered(e, E)) return 0u;
-    float l[3];
-    barycentrics(E, s.A, l);
-    const float zf = interpolate_z(l, z);
-    if (!(zf >= 0.0f && zf < 1.0f)) return 0u;
+// raster_point<Mode::Plain> at the four samples of pixel (x, y), into the caller's surface; the sample fragments that
+// exist (0 .. 4). (Apart from raster_point: profiles/raster_once/samples_in_point_routine.txt.)
+__device__ __forceinline__ uint32_t raster_pixel_samples(const MsaaArgs& m, const Tri& s, const Edges& e,
+                                                         const float z[3], uint32_t prim, int x, int y) {
+    const RasterArgs& a = m.r;
     const int band_h = a.row_end - a.row_begin;
-    const int64_t i = PBR_BOUNDS_PIXEL((int64_t)(y - a.row_begin) * a.stride + x, a.width, band_h, a.stride, 1,
+    const int64_t plane = (int64_t)band_h * m.vis_stride;
+    const int64_t i = PBR_BOUNDS_PIXEL((int64_t)(y - a.row_begin) * m.vis_stride + x, a.width, band_h, m.vis_stride, 1,
                                        kBoundsRaster);
-    if (!(zf < a.depth_in[i])) return kFragment;
-    if (a.prim_in != nullptr && prim < a.prim_in[i]) return kFragment;
-    const unsigned long long key = ((unsigned long long)prim << 32) | (unsigned long long)__float_as_uint(zf);
-    [[maybe_unused]] const int64_t n_vis = (int64_t)band_h * a.width;
-    atomicMin(a.vis + PBR_BOUNDS((int64_t)(y - a.row_begin) * a.width + x, n_vis, kBoundsRaster), key);
-    return kFragment | kFragUpdate;
+    uint32_t frags = 0;
+#pragma unroll
+    for (int sm = 0; sm < kSamples; ++sm) {
+        const int px = 256 * x + 128 + sample_dx(sm), py = 256 * y + 128 + sample_dy(sm);
+        const long long E[3] = {edge_at(e, 0, px, py), edge_at(e, 1, px, py), edge_at(e, 2, px, py)};
+        if (!covered(e, E)) continue;
+        float l[3];
+        barycentrics(E, s.A, l);
+        const float zf = interpolate_z(l, z);
+        if (!(zf >= 0.0f && zf < 1.0f)) continue;
+        const unsigned long long key = ((unsigned long long)__float_as_uint(zf) << 32) | (unsigned long long)prim;
+        atomicMin(m.vis + sm * plane + i, key);
+        ++frags;
+    }
+    return frags;
 }
 
-// A lane's (or workgroup's) counts of a layer call: the fragments that exist and the visibility updates issued.
-struct PeelCounts {
-    uint32_t frags = 0, updates = 0;
-    __device__ __forceinline__ void add(uint32_t r) {
-        frags += r & 1u;
-        updates += r >> 1;
+// The coverage of a triangle (or piece) with a small box, by its setup lane (the unflagged setup kernel keeps its
+// loop written out: profiles/raster_once/small_loop_as_function.txt).
+template <Mode M>
+__device__ __forceinline__ void raster_small(const RasterArgs& a, const Tri& s, const Box& b, const float z[3],
+                                             const AlphaTri* al, uint32_t prim, Counts& n) {
+    Edges e;
+    tri_edges(s, e);
+    if constexpr (M == Mode::Plain) {  // one sum per piece: profiles/raster_once/small_loop_plain_sum.txt
+        uint32_t frags = 0;
+        for (int y = b.y0; y <= b.y1; ++y)
+            for (int x = b.x0; x <= b.x1; ++x) frags += raster_point<M>(a, s, e, z, al, prim, x, y);
+        n.frags += frags;
+    } else {
+        for (int y = b.y0; y <= b.y1; ++y)
+            for (int x = b.x0; x <= b.x1; ++x) n.add<M>(raster_point<M>(a, s, e, z, al, prim, x, y));
     }
-};
+}
 
 // ---- Near-plane clipping (step 2a) ----
 // A piece of a clipped triangle after setup: s as for a triangle, with s.rec[v] the submitted vertex that piece
@@ -427,6 +511,8 @@ __device__ __forceinline__ TriStatus piece_setup(const RasterArgs& a, const Tri&
     }
     if (flags & kVertexNear) return kTriNear;
     if (flags & kVertexGuard) return kTriGuard;
+    // (step 4's end again, with the piece's own per-vertex values: calling tri_area changes the ten CLIP kernels,
+    // profiles/raster_once/piece_setup_calls_tri_area.txt, and they have not been timed against the parent)
     long long A = (long long)(s.X[1] - s.X[0]) * (long long)(s.Y[2] - s.Y[0]) -
                   (long long)(s.X[2] - s.X[0]) * (long long)(s.Y[1] - s.Y[0]);
     if (A == 0) return kTriZeroArea;
@@ -471,6 +557,25 @@ __device__ __forceinline__ void count_wave(unsigned long long* counter, uint32_t
 __device__ __forceinline__ void count_ballot(unsigned long long* counter, bool mine) {
     const uint64_t m = __ballot(mine);
     if ((threadIdx.x & 63u) == 0u && m != 0ull) atomicAdd(counter, (unsigned long long)__popcll(m));
+}
+
+// Appends the wave's large triangles (or pieces: `piece` in the top bit of the block count) to the list: one atomic
+// per wave. Every lane of the wave calls it.
+__device__ __forceinline__ void append_large(const RasterArgs& a, bool large, const Box& b, uint32_t t, uint32_t piece,
+                                             int64_t slots) {
+    const uint64_t m = __ballot(large);
+    if (m != 0ull) {
+        const uint32_t lane = threadIdx.x & 63u;
+        const int leader = (int)__builtin_ctzll(m);
+        unsigned long long base = 0;
+        if ((int)lane == leader) base = atomicAdd(a.counters + kRasterLarge, (unsigned long long)__popcll(m));
+        base = __shfl(base, leader, 64);
+        if (large) {  // the triangle and its block count: a workgroup whose slab has no block of it skips it unread
+            const uint32_t rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+            const uint32_t nb = ((uint32_t)(b.x1 - b.x0) / kBlockW + 1u) * ((uint32_t)(b.y1 - b.y0) / kBlockH + 1u);
+            a.large[PBR_BOUNDS((int64_t)base + rank, slots, kBoundsRaster)] = make_uint2(t, nb | (piece << 31));
+        }
+    }
 }
 
 }  // namespace raster
@@ -524,58 +629,6 @@ __global__ __launch_bounds__(256) void raster_vertex_kernel(const RasterArgs a) 
     a.records[PBR_BOUNDS((int64_t)g, (int64_t)a.n_records, kBoundsRaster)] = o;
 }
 
-namespace raster {
-
-// The two halves of raster_setup_kernel's tail as functions, for raster_setup_clip_kernel's piece loop (the unflagged
-// kernel keeps them written out: its code object is the one pbr_rasterize was measured with).
-// The coverage of a triangle (or piece) with a small box, by its setup lane; the fragments.
-__device__ __forceinline__ uint32_t raster_small(const RasterArgs& a, const Tri& s, const Box& b, const float z[3],
-                                                 uint32_t prim) {
-    Edges e;
-    tri_edges(s, e);
-    uint32_t frags = 0;
-    for (int y = b.y0; y <= b.y1; ++y)
-        for (int x = b.x0; x <= b.x1; ++x) frags += raster_pixel(a, s, e, z, prim, x, y);
-    return frags;
-}
-// The same with the alpha test (step 6a).
-__device__ __forceinline__ void raster_small_alpha(const RasterArgs& a, const Tri& s, const Box& b, const float z[3],
-                                                   const AlphaTri& al, uint32_t prim, FragCounts& n) {
-    Edges e;
-    tri_edges(s, e);
-    for (int y = b.y0; y <= b.y1; ++y)
-        for (int x = b.x0; x <= b.x1; ++x) n.add(raster_pixel_alpha(a, s, e, z, al, prim, x, y));
-}
-// The same for a layer call (step 7a).
-__device__ __forceinline__ void raster_small_peel(const RasterArgs& a, const Tri& s, const Box& b, const float z[3],
-                                                  uint32_t prim, PeelCounts& n) {
-    Edges e;
-    tri_edges(s, e);
-    for (int y = b.y0; y <= b.y1; ++y)
-        for (int x = b.x0; x <= b.x1; ++x) n.add(raster_pixel_peel(a, s, e, z, prim, x, y));
-}
-
-// Appends the wave's large triangles (or pieces: `piece` in the top bit of the block count) to the list: one atomic
-// per wave. Every lane of the wave calls it.
-__device__ __forceinline__ void append_large(const RasterArgs& a, bool large, const Box& b, uint32_t t, uint32_t piece,
-                                             int64_t slots) {
-    const uint64_t m = __ballot(large);
-    if (m != 0ull) {
-        const uint32_t lane = threadIdx.x & 63u;
-        const int leader = (int)__builtin_ctzll(m);
-        unsigned long long base = 0;
-        if ((int)lane == leader) base = atomicAdd(a.counters + kRasterLarge, (unsigned long long)__popcll(m));
-        base = __shfl(base, leader, 64);
-        if (large) {  // the triangle and its block count: a workgroup whose slab has no block of it skips it unread
-            const uint32_t rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-            const uint32_t nb = ((uint32_t)(b.x1 - b.x0) / kBlockW + 1u) * ((uint32_t)(b.y1 - b.y0) / kBlockH + 1u);
-            a.large[PBR_BOUNDS((int64_t)base + rank, slots, kBoundsRaster)] = make_uint2(t, nb | (piece << 31));
-        }
-    }
-}
-
-}  // namespace raster
-
 // Stage 2: setup of every triangle, the statistics, the small triangles' coverage, the large list. ALPHA (a call with
 // PBR_RASTER_ALPHA_TEST some draw of which has a tested material): each lane has its own triangle, so the material
 // record is read per lane, and rw and TexCoord only by the lane of a small triangle of a tested draw. PEEL (a layer
@@ -594,57 +647,41 @@ __global__ __launch_bounds__(256) void raster_setup_kernel(const RasterArgs a) {
     count_ballot(a.counters + kRasterNear, valid && st == kTriNear);
     count_ballot(a.counters + kRasterGuard, valid && st == kTriGuard);
     Box b{0, -1, 0, -1};
-    const bool draw = valid && st == kTriDraw && tri_box(a, s, b);
+    const bool draw = valid && st == kTriDraw && tri_box(a, s, 0, b);
     const long long npix = draw ? (long long)(b.x1 - b.x0 + 1) * (long long)(b.y1 - b.y0 + 1) : 0;
     const bool small = draw && npix <= kSmallPixels, large = draw && !small;
 
-    uint32_t frags = 0;
-    if constexpr (ALPHA) {
-        FragCounts n;
+    constexpr Mode M = mode_of(ALPHA, PEEL);
+    Counts n;
+    if constexpr (M == Mode::Alpha) {
         if (small) {
             float z[3];
             load_z(a, s, z);
             AlphaTri al;
             alpha_material<false>(a, s.draw, al);
             if (al.tested) alpha_vertices(a, s, al);
-            raster_small_alpha(a, s, b, z, al, t, n);
+            raster_small<M>(a, s, b, z, &al, t, n);
         }
-        frags = n.frags;
-        count_wave(a.counters + kRasterAlphaTested, n.tested);
+        count_wave(a.counters + kRasterAlphaTested, n.tested());
         count_wave(a.counters + kRasterAlphaDiscarded, n.discarded);
-    } else if constexpr (PEEL) {
-        PeelCounts n;
+    } else if constexpr (M == Mode::Peel) {
         if (small) {
             float z[3];
             load_z(a, s, z);
-            raster_small_peel(a, s, b, z, t, n);
+            raster_small<M>(a, s, b, z, nullptr, t, n);
         }
-        frags = n.frags;
-        count_wave(a.counters + kRasterLayerFragments, n.updates);
+        count_wave(a.counters + kRasterLayerFragments, n.updates());
     } else if (small) {
         Edges e;
         tri_edges(s, e);
         float z[3];
         load_z(a, s, z);
         for (int y = b.y0; y <= b.y1; ++y)
-            for (int x = b.x0; x <= b.x1; ++x) frags += raster_pixel(a, s, e, z, t, x, y);
+            for (int x = b.x0; x <= b.x1; ++x) n.add<M>(raster_point<M>(a, s, e, z, nullptr, t, x, y));
     }
-    count_wave(a.counters + kRasterFragments, frags);
+    count_wave(a.counters + kRasterFragments, n.frags);
 
-    // one atomic per wave for its large triangles
-    const uint64_t m = __ballot(large);
-    if (m != 0ull) {
-        const uint32_t lane = threadIdx.x & 63u;
-        const int leader = (int)__builtin_ctzll(m);
-        unsigned long long base = 0;
-        if ((int)lane == leader) base = atomicAdd(a.counters + kRasterLarge, (unsigned long long)__popcll(m));
-        base = __shfl(base, leader, 64);
-        if (large) {  // the triangle and its block count: a workgroup whose slab has no block of it skips it unread
-            const uint32_t rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-            const uint32_t nb = ((uint32_t)(b.x1 - b.x0) / kBlockW + 1u) * ((uint32_t)(b.y1 - b.y0) / kBlockH + 1u);
-            a.large[PBR_BOUNDS((int64_t)base + rank, (int64_t)a.n_tris, kBoundsRaster)] = make_uint2(t, nb);
-        }
-    }
+    append_large(a, large, b, t, 0u, (int64_t)a.n_tris);
 }
 
 // Stage 2 with near clipping: the lane of a clipped triangle walks its (at most two) pieces; each is counted,
@@ -666,9 +703,8 @@ __global__ __launch_bounds__(256) void raster_setup_clip_kernel(const RasterArgs
     count_wave(a.counters + kRasterClipPieces, clipped ? (uint32_t)n_pieces : 0u);
     // what the triangle itself adds to the skip counters; its pieces add theirs below
     uint32_t culled = st == kTriCulled, zero = st == kTriZeroArea, near = st == kTriNear, guard = st == kTriGuard;
-    uint32_t frags = 0;
-    [[maybe_unused]] FragCounts n;
-    [[maybe_unused]] PeelCounts np;
+    constexpr Mode M = mode_of(ALPHA, PEEL);
+    Counts n;
     for (int p = 0; p < 2; ++p) {
         Piece P;
         Box b{0, -1, 0, -1};
@@ -682,12 +718,12 @@ __global__ __launch_bounds__(256) void raster_setup_clip_kernel(const RasterArgs
                 ps = kTriDraw;
             }
         }
-        const bool draw = ps == kTriDraw && tri_box(a, P.s, b);
+        const bool draw = ps == kTriDraw && tri_box(a, P.s, 0, b);
         const long long npix = draw ? (long long)(b.x1 - b.x0 + 1) * (long long)(b.y1 - b.y0 + 1) : 0;
         const bool small = draw && npix <= kSmallPixels, large = draw && !small;
         if (small) {
             if (!clipped) load_z(a, P.s, P.z);
-            if constexpr (ALPHA) {
+            if constexpr (M == Mode::Alpha) {
                 AlphaTri al;
                 alpha_material<false>(a, P.s.draw, al);
                 if (al.tested) {
@@ -696,27 +732,23 @@ __global__ __launch_bounds__(256) void raster_setup_clip_kernel(const RasterArgs
                     else
                         alpha_vertices(a, P.s, al);
                 }
-                raster_small_alpha(a, P.s, b, P.z, al, t, n);
-            } else if constexpr (PEEL) {
-                raster_small_peel(a, P.s, b, P.z, t, np);
+                raster_small<M>(a, P.s, b, P.z, &al, t, n);
             } else {
-                frags += raster_small(a, P.s, b, P.z, t);
+                raster_small<M>(a, P.s, b, P.z, nullptr, t, n);
             }
         }
         append_large(a, large, b, t, (uint32_t)p, a.n_large);
     }
-    if constexpr (ALPHA) frags = n.frags;
-    if constexpr (PEEL) frags = np.frags;
     count_wave(a.counters + kRasterCulled, culled);
     count_wave(a.counters + kRasterZeroArea, zero);
     count_wave(a.counters + kRasterNear, near);
     count_wave(a.counters + kRasterGuard, guard);
-    count_wave(a.counters + kRasterFragments, frags);
-    if constexpr (ALPHA) {
-        count_wave(a.counters + kRasterAlphaTested, n.tested);
+    count_wave(a.counters + kRasterFragments, n.frags);
+    if constexpr (M == Mode::Alpha) {
+        count_wave(a.counters + kRasterAlphaTested, n.tested());
         count_wave(a.counters + kRasterAlphaDiscarded, n.discarded);
     }
-    if constexpr (PEEL) count_wave(a.counters + kRasterLayerFragments, np.updates);
+    if constexpr (M == Mode::Peel) count_wave(a.counters + kRasterLayerFragments, n.updates());
 }
 
 // Stage 3: the large triangles. blockIdx.x strides over the list, blockIdx.y over the triangle's 64 x 4 blocks; a wave
@@ -733,9 +765,8 @@ __global__ __launch_bounds__(256) void raster_large_kernel(const RasterArgs a) {
     const unsigned long long listed = a.counters[kRasterLarge];
     const uint32_t slots = CLIP ? (uint32_t)a.n_large : a.n_tris;
     const uint32_t n_large = listed < (unsigned long long)slots ? (uint32_t)listed : slots;
-    uint32_t frags = 0;
-    [[maybe_unused]] FragCounts n;
-    [[maybe_unused]] PeelCounts np;
+    constexpr Mode M = mode_of(ALPHA, PEEL);
+    Counts n;
     for (uint32_t i = blockIdx.x; i < n_large; i += gridDim.x) {
         const uint2 entry = a.large[PBR_BOUNDS((int64_t)i, (int64_t)slots, kBoundsRaster)];
         const uint32_t blocks = CLIP ? entry.y & 0x7FFFFFFFu : entry.y;
@@ -763,9 +794,9 @@ __global__ __launch_bounds__(256) void raster_large_kernel(const RasterArgs a) {
                 if constexpr (ALPHA)
                     if (al.tested) alpha_vertices(a, s, al);
             }
-            if (!tri_box(a, s, b)) continue;
+            if (!tri_box(a, s, 0, b)) continue;
         } else {
-            if (tri_setup(a, t, s) != kTriDraw || !tri_box(a, s, b)) continue;  // never: the setup kernel listed it
+            if (tri_setup(a, t, s) != kTriDraw || !tri_box(a, s, 0, b)) continue;  // never: the setup kernel listed it
         }
         const uint32_t nbx = (uint32_t)(b.x1 - b.x0) / kBlockW + 1u, nby = (uint32_t)(b.y1 - b.y0) / kBlockH + 1u;
         const uint32_t nb = nbx * nby;
@@ -783,29 +814,21 @@ __global__ __launch_bounds__(256) void raster_large_kernel(const RasterArgs a) {
             bool reject = false;
 #pragma unroll
             for (int k = 0; k < 3; ++k) {  // an edge function is linear: its maximum over the block is at a corner
-                const long long m = max(max(edge_at(e, k, X0, Y0), edge_at(e, k, X1, Y0)),
-                                        max(edge_at(e, k, X0, Y1), edge_at(e, k, X1, Y1)));
+                const long long m = max(max(edge_at_centre(e, k, X0, Y0), edge_at_centre(e, k, X1, Y0)),
+                                        max(edge_at_centre(e, k, X0, Y1), edge_at_centre(e, k, X1, Y1)));
                 reject = reject || m < 0;
             }
             if (reject) continue;
             const int x = X0 + (int)(threadIdx.x & 63u), y = Y0 + (int)(threadIdx.x >> 6);
-            if constexpr (ALPHA) {
-                if (x <= X1 && y <= Y1) n.add(raster_pixel_alpha(a, s, e, z, al, t, x, y));
-            } else if constexpr (PEEL) {
-                if (x <= X1 && y <= Y1) np.add(raster_pixel_peel(a, s, e, z, t, x, y));
-            } else {
-                if (x <= X1 && y <= Y1) frags += raster_pixel(a, s, e, z, t, x, y);
-            }
+            if (x <= X1 && y <= Y1) n.add<M>(raster_point<M>(a, s, e, z, &al, t, x, y));
         }
     }
-    if constexpr (ALPHA) frags = n.frags;
-    if constexpr (PEEL) frags = np.frags;
-    count_wave(a.counters + kRasterFragments, frags);
-    if constexpr (ALPHA) {
-        count_wave(a.counters + kRasterAlphaTested, n.tested);
+    count_wave(a.counters + kRasterFragments, n.frags);
+    if constexpr (M == Mode::Alpha) {
+        count_wave(a.counters + kRasterAlphaTested, n.tested());
         count_wave(a.counters + kRasterAlphaDiscarded, n.discarded);
     }
-    if constexpr (PEEL) count_wave(a.counters + kRasterLayerFragments, np.updates);
+    if constexpr (M == Mode::Peel) count_wave(a.counters + kRasterLayerFragments, n.updates());
 }
 
 namespace raster {
@@ -843,7 +866,7 @@ __device__ __forceinline__ bool resolve_clipped(const RasterArgs& a, const Tri& 
         if (piece_setup(a, src, outside, piece, P) != kTriDraw) continue;
         Edges e;
         tri_edges(P.s, e);
-        const long long E[3] = {edge_at(e, 0, x, y), edge_at(e, 1, x, y), edge_at(e, 2, x, y)};
+        const long long E[3] = {edge_at_centre(e, 0, x, y), edge_at_centre(e, 1, x, y), edge_at_centre(e, 2, x, y)};
         if (!covered(e, E)) continue;
         float l[3], p[3], q[3];
         barycentrics(E, P.s.A, l);
@@ -852,9 +875,7 @@ __device__ __forceinline__ bool resolve_clipped(const RasterArgs& a, const Tri& 
         depth = zf;
 #pragma unroll
         for (int v = 0; v < 3; ++v) p[v] = l[v] * P.rw[v];
-        const float sum = (p[0] + p[1]) + p[2];
-#pragma unroll
-        for (int v = 0; v < 3; ++v) q[v] = p[v] / sum;
+        perspective_weights(p, q);
         const RasterVertex *ra[3], *rb[3];
 #pragma unroll
         for (int v = 0; v < 3; ++v) {
@@ -869,7 +890,7 @@ __device__ __forceinline__ bool resolve_clipped(const RasterArgs& a, const Tri& 
                 const float fa = ra[v]->a[k], fb = rb[v]->a[k];
                 av[v] = P.recb[v] == P.s.rec[v] ? fa : fa + P.t[v] * (fb - fa);
             }
-            out[k] = (q[0] * av[0] + q[1] * av[1]) + q[2] * av[2];
+            out[k] = interpolate(q, av[0], av[1], av[2]);
         }
         material = a.draws[PBR_BOUNDS((int64_t)P.s.draw, (int64_t)a.n_draws, kBoundsRaster)].material;
         return true;
@@ -903,7 +924,7 @@ __device__ __forceinline__ void resolve_pixel(const RasterArgs& a, int x, int y,
     }
     Edges e;
     tri_edges(s, e);
-    const long long E[3] = {edge_at(e, 0, x, y), edge_at(e, 1, x, y), edge_at(e, 2, x, y)};
+    const long long E[3] = {edge_at_centre(e, 0, x, y), edge_at_centre(e, 1, x, y), edge_at_centre(e, 2, x, y)};
     float l[3], p[3], q[3];
     barycentrics(E, s.A, l);
     const RasterVertex* r[3];
@@ -913,11 +934,9 @@ __device__ __forceinline__ void resolve_pixel(const RasterArgs& a, int x, int y,
     depth = interpolate_z(l, z);  // the key's z: the same operations on the same values
 #pragma unroll
     for (int v = 0; v < 3; ++v) p[v] = l[v] * r[v]->rw;
-    const float sum = (p[0] + p[1]) + p[2];
+    perspective_weights(p, q);
 #pragma unroll
-    for (int v = 0; v < 3; ++v) q[v] = p[v] / sum;
-#pragma unroll
-    for (int k = 0; k < 14; ++k) out[k] = (q[0] * r[0]->a[k] + q[1] * r[1]->a[k]) + q[2] * r[2]->a[k];
+    for (int k = 0; k < 14; ++k) out[k] = interpolate(q, r[0]->a[k], r[1]->a[k], r[2]->a[k]);
     material = a.draws[PBR_BOUNDS((int64_t)s.draw, (int64_t)a.n_draws, kBoundsRaster)].material;
 }
 
@@ -987,33 +1006,47 @@ __global__ __launch_bounds__(256) void raster_resolve_kernel(const RasterArgs a)
     }
 }
 
+namespace raster {
+
+// A runtime flag as a compile-time one: f(std::true_type) or f(std::false_type).
+template <class F>
+void with_bool(bool flag, F&& f) {
+    if (flag)
+        f(std::true_type{});
+    else
+        f(std::false_type{});
+}
+// The call's mode likewise, as the kernels' (ALPHA, PEEL): a layer call runs no alpha test, so (true, true) is never
+// named and never instantiated.
+template <class F>
+void with_mode(const RasterArgs& a, F&& f) {
+    if (a.peel)
+        f(std::false_type{}, std::true_type{});
+    else
+        with_bool(a.alpha_test, [&](auto alpha) { f(alpha, std::false_type{}); });
+}
+
+}  // namespace raster
+
 hipError_t launch_raster_vertices(const RasterArgs& a, hipStream_t stream) {
     if (a.n_records == 0u) return hipSuccess;
     const dim3 grid((a.n_records + 255u) / 256u);
-    if (a.clip_near)
-        hipLaunchKernelGGL((raster_vertex_kernel<true>), grid, dim3(256), 0, stream, a);
-    else
-        hipLaunchKernelGGL((raster_vertex_kernel<false>), grid, dim3(256), 0, stream, a);
+    raster::with_bool(a.clip_near, [&](auto clip) {
+        hipLaunchKernelGGL((raster_vertex_kernel<decltype(clip)::value>), grid, dim3(256), 0, stream, a);
+    });
     return hipGetLastError();
 }
 
 hipError_t launch_raster_setup(const RasterArgs& a, hipStream_t stream) {
     if (a.n_tris == 0u) return hipSuccess;
     const dim3 grid((uint32_t)(((uint64_t)a.n_tris + 255u) / 256u));
-    if (a.clip_near) {
-        if (a.peel)
-            hipLaunchKernelGGL((raster_setup_clip_kernel<false, true>), grid, dim3(256), 0, stream, a);
-        else if (a.alpha_test)
-            hipLaunchKernelGGL((raster_setup_clip_kernel<true, false>), grid, dim3(256), 0, stream, a);
+    raster::with_mode(a, [&](auto alpha, auto peel) {
+        constexpr bool ALPHA = decltype(alpha)::value, PEEL = decltype(peel)::value;
+        if (a.clip_near)
+            hipLaunchKernelGGL((raster_setup_clip_kernel<ALPHA, PEEL>), grid, dim3(256), 0, stream, a);
         else
-            hipLaunchKernelGGL((raster_setup_clip_kernel<false, false>), grid, dim3(256), 0, stream, a);
-    } else if (a.peel) {
-        hipLaunchKernelGGL((raster_setup_kernel<false, true>), grid, dim3(256), 0, stream, a);
-    } else if (a.alpha_test) {
-        hipLaunchKernelGGL((raster_setup_kernel<true, false>), grid, dim3(256), 0, stream, a);
-    } else {
-        hipLaunchKernelGGL((raster_setup_kernel<false, false>), grid, dim3(256), 0, stream, a);
-    }
+            hipLaunchKernelGGL((raster_setup_kernel<ALPHA, PEEL>), grid, dim3(256), 0, stream, a);
+    });
     return hipGetLastError();
 }
 
@@ -1021,20 +1054,12 @@ hipError_t launch_raster_large(const RasterArgs& a, hipStream_t stream) {
     if (a.n_tris == 0u) return hipSuccess;
     const uint32_t gx = a.n_tris < (uint32_t)raster::kLargeGridX ? a.n_tris : (uint32_t)raster::kLargeGridX;
     const dim3 grid(gx, raster::kLargeSlabs);
-    if (a.clip_near) {
-        if (a.peel)
-            hipLaunchKernelGGL((raster_large_kernel<true, false, true>), grid, dim3(256), 0, stream, a);
-        else if (a.alpha_test)
-            hipLaunchKernelGGL((raster_large_kernel<true, true, false>), grid, dim3(256), 0, stream, a);
-        else
-            hipLaunchKernelGGL((raster_large_kernel<true, false, false>), grid, dim3(256), 0, stream, a);
-    } else if (a.peel) {
-        hipLaunchKernelGGL((raster_large_kernel<false, false, true>), grid, dim3(256), 0, stream, a);
-    } else if (a.alpha_test) {
-        hipLaunchKernelGGL((raster_large_kernel<false, true, false>), grid, dim3(256), 0, stream, a);
-    } else {
-        hipLaunchKernelGGL((raster_large_kernel<false, false, false>), grid, dim3(256), 0, stream, a);
-    }
+    raster::with_bool(a.clip_near, [&](auto clip) {
+        raster::with_mode(a, [&](auto alpha, auto peel) {
+            constexpr bool CLIP = decltype(clip)::value, ALPHA = decltype(alpha)::value, PEEL = decltype(peel)::value;
+            hipLaunchKernelGGL((raster_large_kernel<CLIP, ALPHA, PEEL>), grid, dim3(256), 0, stream, a);
+        });
+    });
     return hipGetLastError();
 }
 
@@ -1042,92 +1067,23 @@ hipError_t launch_raster_resolve(const RasterArgs& a, hipStream_t stream) {
     const int band_h = a.row_end - a.row_begin;
     if (a.width <= 0 || band_h <= 0) return hipSuccess;
     const dim3 grid((a.width + 63) / 64, (band_h + 7) / 8);
-    if (a.peel) {
-        if (a.clip_near) {
-            if (a.vec)
-                hipLaunchKernelGGL((raster_resolve_kernel<true, true, true>), grid, dim3(256), 0, stream, a);
-            else
-                hipLaunchKernelGGL((raster_resolve_kernel<false, true, true>), grid, dim3(256), 0, stream, a);
-        } else if (a.vec) {
-            hipLaunchKernelGGL((raster_resolve_kernel<true, false, true>), grid, dim3(256), 0, stream, a);
-        } else {
-            hipLaunchKernelGGL((raster_resolve_kernel<false, false, true>), grid, dim3(256), 0, stream, a);
-        }
-    } else if (a.clip_near) {
-        if (a.vec)
-            hipLaunchKernelGGL((raster_resolve_kernel<true, true, false>), grid, dim3(256), 0, stream, a);
-        else
-            hipLaunchKernelGGL((raster_resolve_kernel<false, true, false>), grid, dim3(256), 0, stream, a);
-    } else if (a.vec) {
-        hipLaunchKernelGGL((raster_resolve_kernel<true, false, false>), grid, dim3(256), 0, stream, a);
-    } else {
-        hipLaunchKernelGGL((raster_resolve_kernel<false, false, false>), grid, dim3(256), 0, stream, a);
-    }
+    raster::with_bool(a.vec, [&](auto vec) {
+        raster::with_bool(a.clip_near, [&](auto clip) {
+            raster::with_bool(a.peel, [&](auto peel) {
+                constexpr bool VEC = decltype(vec)::value, CLIP = decltype(clip)::value, PEEL = decltype(peel)::value;
+                hipLaunchKernelGGL((raster_resolve_kernel<VEC, CLIP, PEEL>), grid, dim3(256), 0, stream, a);
+            });
+        });
+    });
     return hipGetLastError();
 }
 
 // ---- Four samples per pixel (step 7b; pbr_msaa_rasterize, pbr_msaa_fragments) -------------------------------------
-// Kernels of their own beside the 1x ones (as raster_setup_clip_kernel is beside raster_setup_kernel), built from the
-// same helpers: the 1x kernels above are not touched. Coverage and depth are steps 5-6 at the four sample points of a
-// pixel, D3D's standard pattern in 1/16 pixel, which lies on the 1/256 grid; visibility is step 7's key lowered by
-// atomicMin into one word per (sample, pixel) of the caller's surface, sample-major. The fragments stage takes the
-// resolve's place: the samples of a pixel with the same triangle are one fragment, numbered as slots by their lowest
-// sample; slot k's attributes are step 8 at the pixel centre, whether or not the centre is covered.
-namespace raster {
-
-constexpr int kSamples = 4;
-constexpr int kSampleReach = 96;  // no sample is further from its pixel's centre, in subpixels, along either axis
-
-// Sample s of a pixel is at (256 x + 128 + sample_dx(s), 256 y + 128 + sample_dy(s)):
-// (-2, -6), (6, -2), (-6, 2), (2, 6) sixteenths of a pixel.
-__device__ __forceinline__ int sample_dx(int s) { return s == 0 ? -32 : (s == 1 ? 96 : (s == 2 ? -96 : 32)); }
-__device__ __forceinline__ int sample_dy(int s) { return s == 0 ? -96 : (s == 1 ? -32 : (s == 2 ? 32 : 96)); }
-
-// edge_at for any point of the subpixel grid.
-__device__ __forceinline__ long long edge_at_point(const Edges& e, int k, int px, int py) {
-    return (long long)e.dx[k] * (long long)(py - e.ya[k]) - (long long)e.dy[k] * (long long)(px - e.xa[k]);
-}
-
-// tri_box for sample points: the pixels that can have a sample inside the triangle's bounding box, clipped to the
-// band. Conservative: every point within kSampleReach of the centre counts, whether a sample sits there or not.
-__device__ __forceinline__ bool tri_box_samples(const RasterArgs& a, const Tri& s, Box& b) {
-    const int minx = min(s.X[0], min(s.X[1], s.X[2])), maxx = max(s.X[0], max(s.X[1], s.X[2]));
-    const int miny = min(s.Y[0], min(s.Y[1], s.Y[2])), maxy = max(s.Y[0], max(s.Y[1], s.Y[2]));
-    // 256 p + 128 + 96 >= min and 256 p + 128 - 96 <= max
-    b.x0 = max((minx - (128 + kSampleReach) + 255) >> 8, 0);
-    b.x1 = min((maxx - (128 - kSampleReach)) >> 8, a.width - 1);
-    b.y0 = max((miny - (128 + kSampleReach) + 255) >> 8, a.row_begin);
-    b.y1 = min((maxy - (128 - kSampleReach)) >> 8, a.row_end - 1);
-    return b.x0 <= b.x1 && b.y0 <= b.y1;
-}
-
-// raster_pixel for the four samples of pixel (x, y); the sample fragments that exist (0 .. 4).
-__device__ __forceinline__ uint32_t raster_pixel_samples(const MsaaArgs& m, const Tri& s, const Edges& e,
-                                                         const float z[3], uint32_t prim, int x, int y) {
-    const RasterArgs& a = m.r;
-    const int band_h = a.row_end - a.row_begin;
-    const int64_t plane = (int64_t)band_h * m.vis_stride;
-    const int64_t i = PBR_BOUNDS_PIXEL((int64_t)(y - a.row_begin) * m.vis_stride + x, a.width, band_h, m.vis_stride, 1,
-                                       kBoundsRaster);
-    uint32_t frags = 0;
-#pragma unroll
-    for (int sm = 0; sm < kSamples; ++sm) {
-        const int px = 256 * x + 128 + sample_dx(sm), py = 256 * y + 128 + sample_dy(sm);
-        const long long E[3] = {edge_at_point(e, 0, px, py), edge_at_point(e, 1, px, py), edge_at_point(e, 2, px, py)};
-        if (!covered(e, E)) continue;
-        float l[3];
-        barycentrics(E, s.A, l);
-        const float zf = interpolate_z(l, z);
-        if (!(zf >= 0.0f && zf < 1.0f)) continue;
-        const unsigned long long key = ((unsigned long long)__float_as_uint(zf) << 32) | (unsigned long long)prim;
-        atomicMin(m.vis + sm * plane + i, key);
-        ++frags;
-    }
-    return frags;
-}
-
-}  // namespace raster
-
+// Coverage and depth are steps 5-6 at the four sample points of a pixel, D3D's standard pattern in 1/16 pixel, which
+// lies on the 1/256 grid; visibility is step 7's key lowered by atomicMin into one word per (sample, pixel) of the
+// caller's surface, sample-major. The setup and large kernels follow raster_setup_kernel<false, false> and
+// raster_large_kernel<false, false, false> with the sample box (tri_box with kSampleReach) and the sample routine
+// (profiles/raster_once/kernel_body_as_function.txt keeps the flows apart).
 // Stage 2 for samples: raster_setup_kernel's flow with the sample box: a triangle whose box of pixels with reachable
 // samples holds at most kSmallPixels pixels is rasterised by its lane (at most 4 kSmallPixels sample tests), the others
 // are listed. A triangle that covers a sample but no pixel centre has an empty centre box and a non-empty sample box.
@@ -1144,7 +1100,7 @@ __global__ __launch_bounds__(256) void raster_setup_msaa_kernel(const MsaaArgs m
     count_ballot(a.counters + kRasterNear, valid && st == kTriNear);
     count_ballot(a.counters + kRasterGuard, valid && st == kTriGuard);
     Box b{0, -1, 0, -1};
-    const bool draw = valid && st == kTriDraw && tri_box_samples(a, s, b);
+    const bool draw = valid && st == kTriDraw && tri_box(a, s, kSampleReach, b);
     const long long npix = draw ? (long long)(b.x1 - b.x0 + 1) * (long long)(b.y1 - b.y0 + 1) : 0;
     const bool small = draw && npix <= kSmallPixels, large = draw && !small;
     uint32_t frags = 0;
@@ -1176,7 +1132,7 @@ __global__ __launch_bounds__(256) void raster_large_msaa_kernel(const MsaaArgs m
         const uint32_t t = entry.x;
         Tri s;
         Box b;
-        if (tri_setup(a, t, s) != kTriDraw || !tri_box_samples(a, s, b)) continue;  // never: the setup kernel listed it
+        if (tri_setup(a, t, s) != kTriDraw || !tri_box(a, s, kSampleReach, b)) continue;  // never: setup listed it
         const uint32_t nbx = (uint32_t)(b.x1 - b.x0) / kBlockW + 1u, nby = (uint32_t)(b.y1 - b.y0) / kBlockH + 1u;
         const uint32_t nb = nbx * nby;
         if (blockIdx.y >= nb) continue;
@@ -1192,8 +1148,8 @@ __global__ __launch_bounds__(256) void raster_large_msaa_kernel(const MsaaArgs m
             bool reject = false;
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
-                const long long mx = max(max(edge_at_point(e, k, px0, py0), edge_at_point(e, k, px1, py0)),
-                                         max(edge_at_point(e, k, px0, py1), edge_at_point(e, k, px1, py1)));
+                const long long mx = max(max(edge_at(e, k, px0, py0), edge_at(e, k, px1, py0)),
+                                         max(edge_at(e, k, px0, py1), edge_at(e, k, px1, py1)));
                 reject = reject || mx < 0;
             }
             if (reject) continue;
@@ -1244,7 +1200,7 @@ __device__ __forceinline__ int fragments_pixel(const MsaaArgs& m, int x, int y, 
     }
     Edges e;
     tri_edges(s, e);
-    const long long E[3] = {edge_at(e, 0, x, y), edge_at(e, 1, x, y), edge_at(e, 2, x, y)};
+    const long long E[3] = {edge_at_centre(e, 0, x, y), edge_at_centre(e, 1, x, y), edge_at_centre(e, 2, x, y)};
     float l[3], p[3], q[3];
     barycentrics(E, s.A, l);  // at the centre, inside the triangle or not: no clamp
     const RasterVertex* r[3];
@@ -1253,11 +1209,9 @@ __device__ __forceinline__ int fragments_pixel(const MsaaArgs& m, int x, int y, 
     depth = __uint_as_float((uint32_t)(k64 >> 32));
 #pragma unroll
     for (int v = 0; v < 3; ++v) p[v] = l[v] * r[v]->rw;
-    const float sum = (p[0] + p[1]) + p[2];
+    perspective_weights(p, q);
 #pragma unroll
-    for (int v = 0; v < 3; ++v) q[v] = p[v] / sum;
-#pragma unroll
-    for (int k = 0; k < 14; ++k) out[k] = (q[0] * r[0]->a[k] + q[1] * r[1]->a[k]) + q[2] * r[2]->a[k];
+    for (int k = 0; k < 14; ++k) out[k] = interpolate(q, r[0]->a[k], r[1]->a[k], r[2]->a[k]);
     material = a.draws[PBR_BOUNDS((int64_t)s.draw, (int64_t)a.n_draws, kBoundsRaster)].material;
     return n;
 }
@@ -1335,10 +1289,9 @@ hipError_t launch_msaa_fragments(const MsaaArgs& m, hipStream_t stream) {
     const int band_h = m.r.row_end - m.r.row_begin;
     if (m.r.width <= 0 || band_h <= 0) return hipSuccess;
     const dim3 grid((m.r.width + 63) / 64, (band_h + 7) / 8);
-    if (m.r.vec)
-        hipLaunchKernelGGL((raster_fragments_msaa_kernel<true>), grid, dim3(256), 0, stream, m);
-    else
-        hipLaunchKernelGGL((raster_fragments_msaa_kernel<false>), grid, dim3(256), 0, stream, m);
+    raster::with_bool(m.r.vec, [&](auto vec) {
+        hipLaunchKernelGGL((raster_fragments_msaa_kernel<decltype(vec)::value>), grid, dim3(256), 0, stream, m);
+    });
     return hipGetLastError();
 }
 
